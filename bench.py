@@ -14,11 +14,14 @@ the reference's fixed set (fov3dgs/render_compose_gazes_fps.py:26: centre + 8 of
 depend on --steps / --warmup. With N ranks each rank renders its own camera of an 8-camera ring (weak scaling; the views
 are independent: no data-path collective unless --gather).
 
-The K timed steps are run `--repeats` (5) times, each repeat bracketed by barrier + synchronize: value / ms_per_step are the
-MEDIAN repeat, value_spread = [slowest, fastest]. Inside the timed frames only the HIP events around the slowest stage (found
-in an untimed pass first) and around the blend stage are recorded; the other stages' times come from an untimed pass of the
-same frames (an event record is a command on the stream: all eight per frame cost 3.5 %).
-Besides `value` the line carries
+A plain run (no --full) does only what `value` needs: set up, warm up, exactly K timed steps (one repeat unless --repeats says
+otherwise), --dump-outputs if given, and the line (value, ms_per_step, value_raw, value_spread, config).
+With --full the K timed steps are run `--repeats` (5) times, each repeat bracketed by barrier + synchronize: value / ms_per_step
+are the MEDIAN repeat, value_spread = [slowest, fastest]. Inside the timed frames only the HIP events around the slowest stage
+(found in an untimed pass first) and around the blend stage are recorded; the other stages' times come from an untimed pass of
+the same frames (an event record is a command on the stream: all eight per frame cost 3.5 %).
+--dump-outputs DIR: after the headline's timed steps, what the last timed render() call returned (dump_outputs()).
+Besides `value` the line of a --full run carries
   value_packed  the same frames with render(packed="auto") (static-model layout, bit-identical image; fovraster.h)
   value_pipelined  the same frames, the reference's tensors, TWO frames in flight (render_begin / finish on two streams: the head
                 of frame n + 1 is enqueued before frame n's instance count is waited for; images bit-identical). Throughput
@@ -50,6 +53,45 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 GAZES = [(0.25 * i, 0.25 * j) for i in range(1, 4) for j in range(1, 4)]  # render_compose_gazes_fps.py:26
 PROFILE_TAG = "r06"
+METRIC = "frames/sec at 1080p foveated (bicycle-scale)"
+VALUE_NOTE = ("value / ms_per_step: the K timed frames (barrier + synchronize on both sides) with the nine gazes weighted EQUALLY -- "
+              "mean over the gazes of the mean time of that gaze's frames inside the region -- so that it does not depend on steps % 9; "
+              "value_raw / ms_per_step_raw: K / the region's wall clock (gaze i % 9: steps % 9 gazes weigh one frame more)")
+DUMP_BUDGET = 64 * 10 ** 6  # bytes: all files of one --dump-outputs
+DUMP_ROWS = 1 << 19  # per-Gaussian arrays: a fixed, seeded sample of this many rows
+
+
+def workload_name(cloud_name, world, gather):
+    return (cloud_name + " bicycle-scale cloud, 4-layer foveated render (fov_pcheck_obb), the reference's 9 fixed gazes "
+            "(0.25 i, 0.25 j) in turn, one camera per GPU" + (", frames gathered on rank 0" if (world > 1 and gather) else ""))
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the dict the last timed render() call returned, as float32 DIR/<name>.npy. `render` whole (a seeded sample of
+    its pixels, listed in pixel_index.npy, only if the image alone would not fit DUMP_BUDGET); radii, visibility_filter and
+    viewspace_points at a fixed, seeded sample of DUMP_ROWS Gaussians (gaussian_index.npy, float64). Same arguments -> same rows."""
+    import numpy as np
+    import torch
+    if out["render"].is_cuda:
+        torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    P = int(out["radii"].shape[0])
+    idx = np.arange(P) if P <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(P, DUMP_ROWS, replace=False))
+    rows = torch.from_numpy(idx).to(out["radii"].device)
+    arrays = {"gaussian_index": idx.astype(np.float64)}
+    for k in ("radii", "visibility_filter", "viewspace_points"):
+        arrays[k] = out[k].detach().index_select(0, rows).float().cpu().numpy()
+    img = out["render"].detach().float().cpu().numpy()
+    room = DUMP_BUDGET - sum(a.nbytes for a in arrays.values()) - (1 << 20)
+    if img.nbytes > room:
+        n_px = room // (img.shape[0] * 4 + 8)
+        px = np.sort(np.random.default_rng(1).choice(img.shape[1] * img.shape[2], n_px, replace=False))
+        arrays["pixel_index"] = px.astype(np.float64)
+        img = img.reshape(img.shape[0], -1)[:, px]
+    arrays["render"] = img
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log(f"[bench] outputs of the last timed step -> {dirname}: " + ", ".join(f"{k} {a.shape}" for k, a in arrays.items()))
 
 
 def parse_args(argv=None):
@@ -65,9 +107,17 @@ def parse_args(argv=None):
                          "reports S-6M-T under extra.translucent")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K timed steps are run this many times (each bracketed by barrier + synchronize); value = the median "
-                         "repeat, value_spread = [min, max] (one 16 ms region cannot rank two builds)")
+                         "repeat, value_spread = [min, max] (one 16 ms region cannot rank two builds). Default: 1 in a plain run "
+                         "(exactly K timed steps), 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: serial / packed / two-in-flight frames, per-stage times, roofline, "
+                         "CPU baseline, extra (reference protocol, S-6M-T, training step), multi-GPU extras. A plain run times "
+                         "the headline frames only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed render() call returned as DIR/<name>.npy "
+                         "(float32; per-Gaussian arrays at a fixed, seeded sample of rows: dump_outputs())")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--packed-only", action="store_true", help="time only the packed-model frames (profiling passes)")
@@ -87,7 +137,12 @@ def parse_args(argv=None):
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch / rendezvous only (gloo without a GPU): rank 0 prints a line with n_gpus and exits")
     ap.add_argument("--master-port", type=int, default=0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.mode != "render":
+        ap.error("--dump-outputs: the render mode's frames only")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 class Timed(tuple):
@@ -272,6 +327,7 @@ def main():
     frame = frame_of(scene)
 
     settled = set()
+    last = {}  # --dump-outputs: "out" = what the last timed frame of the latest timed_run returned
 
     def timed_run(packed, event_stages, frame=frame, repeats=None):
         """W warm-ups + `repeats` x exactly K timed frames (gaze i % 9), barrier + synchronize on both sides of every repeat.
@@ -331,6 +387,8 @@ def main():
                     for k in event_stages:
                         per_stage[k].append(row[k])
                 timer.close()
+            if args.dump_outputs:
+                last["out"] = out
         mid = int(np.argsort(balanced)[len(balanced) // 2])
         return Timed(balanced[mid], [min(balanced), max(balanced)], {k: float(np.mean(v)) for k, v in per_stage.items()}, times[mid])
 
@@ -391,6 +449,28 @@ def main():
             return _stage_pass(*a_, **k_)
         finally:
             rz_mod.OVERLAP_SUCCESSIVE_FRAMES = overlap_default
+
+    if not args.full:
+        # a plain run: the headline frames only (render() as a caller gets it, no stage events inside them)
+        headline = timed_run("auto" if args.packed_only else None, ())
+        elapsed, spread, _ = headline
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, last.pop("out"))
+        if rank == 0:
+            print(json.dumps(_finite({
+                "metric": METRIC, "value": round(world * K / elapsed, 3), "unit": "frames/s",
+                "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(elapsed / K * 1e3, 4),
+                "value_raw": round(world * K / headline.raw, 3), "ms_per_step_raw": round(headline.raw / K * 1e3, 4),
+                "value_note": VALUE_NOTE, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                "data": "synthetic", "repeats": max(1, args.repeats),
+                "value_spread": [round(world * K / spread[1], 3), round(world * K / spread[0], 3)],
+                "config": {"workload": workload_name(cloud_name, world, args.gather), "gaussians": args.points, "width": W, "height": H,
+                           "alpha": 0.05, "sh_degree": 3, "model_layout": "packed (render(packed=\"auto\"))" if args.packed_only else
+                           "the reference's tensor interface (render(packed=None))",
+                           "overlap_successive_frames": overlap_default, "parallelism": f"views{world}"},
+                "full": False})), flush=True)
+        return
+
     with torch.no_grad():
         for i in range(3):
             frame(GAZES[i % 9], "auto" if args.packed_only else None)
@@ -399,6 +479,8 @@ def main():
     ev_stages = tuple(dict.fromkeys((dominant, "render")))
     if args.packed_only:
         headline = serial = timed_run("auto", ev_stages)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, last.pop("out"))
         elapsed_p, spread_p, timed_ms_p = headline
         elapsed, spread, timed_ms, elapsed_raw = elapsed_p, spread_p, timed_ms_p, headline.raw
         timed_ms_overlapped = timed_ms
@@ -412,6 +494,8 @@ def main():
         # cache write-back on its stream, and three frames share the GPU here (with the two stages' four records per frame the same
         # frames ran 8 % slower)
         headline = timed_run(None, ()) if overlap_default else serial
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, last.pop("out"))
         elapsed, spread, timed_ms_overlapped = headline
         timed_ms = serial[2]
         elapsed_raw = headline.raw
@@ -574,7 +658,7 @@ def main():
             cpu = dict(value=None, unit="frames/s", cores=os.cpu_count(), kind="port", sample=f"failed: {e}")
 
     line = {
-        "metric": "frames/sec at 1080p foveated (bicycle-scale)", "value": round(world * K / elapsed, 3), "unit": "frames/s",
+        "metric": METRIC, "value": round(world * K / elapsed, 3), "unit": "frames/s",
         "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(ms_step, 4),
         "value_raw": round(world * K / elapsed_raw, 3), "ms_per_step_raw": round(elapsed_raw / K * 1e3, 4),
         "value_serial": round(world * K / serial[0], 3), "ms_per_step_serial": round(serial[0] / K * 1e3, 4),
@@ -584,9 +668,7 @@ def main():
                         "n + 1 (cull, projection, counts) runs beside the tail of call n (emission, sort, blend): rasterizer.OVERLAP_SUCCESSIVE_FRAMES = "
                         + str(overlap_default) + "; images bit-identical. value_serial: the same K frames with that switch off (every kernel of a frame alone on the GPU: "
                         "the roofline's kernel durations are measured there)",
-        "value_note": "value / ms_per_step: the K timed frames (barrier + synchronize on both sides) with the nine gazes weighted EQUALLY -- "
-                      "mean over the gazes of the mean time of that gaze's frames inside the region -- so that it does not depend on steps % 9; "
-                      "value_raw / ms_per_step_raw: K / the region's wall clock (gaze i % 9: steps % 9 gazes weigh one frame more)",
+        "value_note": VALUE_NOTE,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "repeats": max(1, args.repeats), "value_spread": [round(world * K / spread[1], 3), round(world * K / spread[0], 3)],
         "value_packed": round(world * K / elapsed_p, 3), "ms_per_step_packed": round(elapsed_p / K * 1e3, 4),
@@ -594,8 +676,7 @@ def main():
         "value_pipelined": round(world * K / elapsed_pl, 3), "ms_per_step_pipelined": round(elapsed_pl / K * 1e3, 4),
         "value_pipelined_spread": [round(world * K / spread_pl[1], 3), round(world * K / spread_pl[0], 3)],
         "pipeline_depth": 2,
-        "config": {"workload": cloud_name + " bicycle-scale cloud, 4-layer foveated render (fov_pcheck_obb), the reference's 9 fixed gazes "
-                               "(0.25 i, 0.25 j) in turn, one camera per GPU" + (", frames gathered on rank 0" if (world > 1 and args.gather) else ""),
+        "config": {"workload": workload_name(cloud_name, world, args.gather),
                    "gaussians": P, "width": W, "height": H, "alpha": 0.05, "sh_degree": 3,
                    "visible": int(st["V"]), "candidates": int(st["C"]), "in_front": V_in, "instances": int(st["D"]),
                    "instances_blend_tiles": int(st["D_blend"]), "max_tile_list": int(max(s["max_list"] for s in stats)),

@@ -3,7 +3,8 @@ of the session, so that the numbers behind "within tolerance" are kept, not just
 session can never overwrite what a GPU session measured (round 3 lost its whole-frame report that way):
   tests/parity_report_gpu.json   written only when a test marked `gpu` recorded a comparison (HIP path vs oracle)
   tests/parity_report_cpu.json   everything a session without GPU comparisons recorded (oracle vs golden vectors)
-(+ the same file under gpurun_out/ when that directory exists, which is how a GPU box's report comes home)."""
+A session writes them into tests/reports/ (kept out of git, so that a test run leaves the tree as it was), or into the directory
+FOVRASTER_PARITY_REPORT_DIR names (=tests refreshes the committed records)."""
 import json
 import os
 
@@ -40,10 +41,10 @@ def flush():
                entries=_entries)
     doc["summary"]["session"] = "gpu" if _gpu_session else "cpu"
     fname = "parity_report_gpu.json" if _gpu_session else "parity_report_cpu.json"
-    for d in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "gpurun_out")):
-        if os.path.isdir(d):
-            try:
-                with open(os.path.join(d, fname), "w") as f:
-                    json.dump(doc, f, indent=1)
-            except OSError:
-                pass
+    d = os.environ.get("FOVRASTER_PARITY_REPORT_DIR") or os.path.join(ROOT, "tests", "reports")
+    try:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, fname), "w") as f:
+            json.dump(doc, f, indent=1)
+    except OSError:
+        pass

@@ -18,13 +18,13 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles; mkdir -p $OUT
 SHA=$(sha256sum fov-3dgs_amd/libfovraster_hip.so | cut -c1-16)
 rm -rf /tmp/prof_h /tmp/prof_o /tmp/prof_a /tmp/prof_t /tmp/prof_f /tmp/prof_w /tmp/prof_pf /tmp/prof_pw /tmp/prof_tf /tmp/prof_tw
 # (--serial-only: one frame on the GPU at a time -- a kernel's duration and counters are its own; the default run overlaps successive frames)
-HEAD="--headline-only --no-extra --no-cpu-baseline --serial-only"
+HEAD="--full --headline-only --no-extra --no-cpu-baseline --serial-only"
 TRAIN="--mode train --steps 20 --warmup 5"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_h -o h -- python3 bench.py $HEAD > /tmp/prof_h.log 2>&1
 cp /tmp/prof_h/h_kernel_stats.csv $OUT/${TAG}_headline_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_o -o o -- python3 bench.py --headline-only --no-extra --no-cpu-baseline > /tmp/prof_o.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_o -o o -- python3 bench.py --full --headline-only --no-extra --no-cpu-baseline > /tmp/prof_o.log 2>&1
 cp /tmp/prof_o/o_kernel_stats.csv $OUT/${TAG}_overlapped_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_a -o b -- python3 bench.py --no-cpu-baseline > /tmp/prof_a.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_a -o b -- python3 bench.py --full --no-cpu-baseline > /tmp/prof_a.log 2>&1
 cp /tmp/prof_a/b_kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv
 grep '^{"metric"' /tmp/prof_a.log | tail -1 > $OUT/${TAG}_bench_line_profiled.json
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_t -o t -- python3 bench.py $TRAIN > /tmp/prof_t.log 2>&1
@@ -32,8 +32,8 @@ cp /tmp/prof_t/t_kernel_stats.csv $OUT/${TAG}_train_kernel_stats.csv
 grep '^{"metric"' /tmp/prof_t.log | tail -1 > $OUT/${TAG}_train_line_profiled.json
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/prof_f -o p -- python3 bench.py $HEAD > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/prof_w -o p -- python3 bench.py $HEAD > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/prof_pf -o p -- python3 bench.py --packed-only --serial-only --no-extra --no-cpu-baseline --steps 18 --repeats 1 > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/prof_pw -o p -- python3 bench.py --packed-only --serial-only --no-extra --no-cpu-baseline --steps 18 --repeats 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/prof_pf -o p -- python3 bench.py --full --packed-only --serial-only --no-extra --no-cpu-baseline --steps 18 --repeats 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/prof_pw -o p -- python3 bench.py --full --packed-only --serial-only --no-extra --no-cpu-baseline --steps 18 --repeats 1 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/prof_tf -o p -- python3 bench.py $TRAIN > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/prof_tw -o p -- python3 bench.py $TRAIN > /dev/null 2>&1
 python3 - "$TAG" "$SHA" <<'PY'
@@ -129,7 +129,7 @@ print(json.dumps(calibration)[:400])
 for n in ("k_project", "k_bin", "k_emit", "k_render_fov"):
     print(n, kernels.get(n))
 PY
-tools/sq_counters.sh $TAG --steps 27 --warmup 9 --no-extra --no-cpu-baseline --headline-only --serial-only --repeats 1 | tail -3
+tools/sq_counters.sh $TAG --full --steps 27 --warmup 9 --no-extra --no-cpu-baseline --headline-only --serial-only --repeats 1 | tail -3
 # 4) the same on S-6M-T (the list-consuming cloud): kernel stats of its foveated frames and of its training step, the whole bench line
 #    on it (counts: blend pairs of every blend kernel), SQ passes over both -> ${TAG}_valu_per_pair.json: vector instructions per
 #    blended (band, entry) pair of k_render_fov, k_render<1,2> and k_render_bwd on both clouds
@@ -138,8 +138,8 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_th -o h -- pyt
 cp /tmp/prof_th/h_kernel_stats.csv $OUT/${TAG}_translucent_headline_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_tt -o t -- python3 bench.py --cloud S-6M-T $TRAIN > /tmp/prof_tt.log 2>&1
 cp /tmp/prof_tt/t_kernel_stats.csv $OUT/${TAG}_translucent_train_kernel_stats.csv
-python3 bench.py --cloud S-6M-T --no-cpu-baseline 2> /dev/null | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench_line_translucent.json
-tools/sq_counters.sh ${TAG}T --cloud S-6M-T --steps 27 --warmup 9 --no-extra --no-cpu-baseline --headline-only --serial-only --repeats 1 | tail -1
+python3 bench.py --full --cloud S-6M-T --no-cpu-baseline 2> /dev/null | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench_line_translucent.json
+tools/sq_counters.sh ${TAG}T --cloud S-6M-T --full --steps 27 --warmup 9 --no-extra --no-cpu-baseline --headline-only --serial-only --repeats 1 | tail -1
 tools/sq_counters.sh ${TAG}train --mode train --steps 12 --warmup 4 | tail -1
 tools/sq_counters.sh ${TAG}Ttrain --cloud S-6M-T --mode train --steps 12 --warmup 4 | tail -1
 python3 - "$TAG" <<'PY'

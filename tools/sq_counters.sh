@@ -4,7 +4,7 @@
 # Each pass is its own rocprofv3 run (--kernel-trace --pmc only; 8 SQ slots + 2 GRBM slots per pass), the program
 # directly after `--`. Per-launch averages for every fr:: kernel; derived figures for the blend kernels.
 TAG=${1:-r02}; shift
-ARGS=${@:---steps 12 --warmup 4 --no-extra --no-cpu-baseline}
+ARGS=${@:---full --steps 12 --warmup 4 --no-extra --no-cpu-baseline}
 cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:?run through gpurun (GRAFT_REPO_ROOT is unset)}"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles; mkdir -p $OUT
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
