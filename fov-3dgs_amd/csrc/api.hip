@@ -478,6 +478,16 @@ int fr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const
 	return launch_l1_ssim_backward(C, H, W, img, target, dmaps, w_l1, w_ssim, grad_scale, dL_dimg, (hipStream_t)stream);
 }
 
+size_t fr_knn_workspace_bytes(int32_t P) { return knn_workspace_bytes(P); }
+
+int fr_knn_mean_dist2(int32_t P, const float *points, float *mean_dist2, void *workspace, void *stream)
+{
+	if (P < 0 || (P > 0 && (!points || !mean_dist2 || !workspace))) { set_error("bad knn_mean_dist2 arguments (P=%d)", P); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	if ((uintptr_t)workspace % 16) { set_error("knn workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	return launch_knn(P, points, mean_dist2, workspace, (hipStream_t)stream);
+}
+
 int fr_backward(const fr_backward_args *a)
 {
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }

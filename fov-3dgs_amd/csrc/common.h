@@ -465,6 +465,8 @@ int launch_l1_ssim_backward(int C, int H, int W, const float *x, const float *y,
 int launch_activate_forward(int P, const float *rs, const float *rq, const float *ro, float *s, float *q, float *o, hipStream_t stream);
 int launch_activate_backward(int P, const float *rs, const float *rq, const float *ro, const float *gs, const float *gq, const float *go,
 	float *ds, float *dq, float *dop, hipStream_t stream);
+size_t knn_workspace_bytes(int P); // knn.hip
+int launch_knn(int P, const float *pts, float *out, void *ws, hipStream_t stream);
 int launch_project(FwdCtx &c); // cull pass + the ordered compaction of its survivors
 int launch_bin(FwdCtx &c);    // projection of the cull pass's survivors, tile counts, colours, item rows
 int launch_tile_scan(FwdCtx &c);

@@ -134,6 +134,35 @@ def save_ply(path, cloud, indexes=None):
         f.write(arr.tobytes())
 
 
+def cloud_from_points(points, colors, sh_degree=3, device="cuda"):
+    """GaussianModel.create_from_pcd (fov3dgs/scene/gaussian_model.py:245-267): a model initialised from a point cloud.
+
+    points [P,3], colors [P,3] in [0, 1] (numpy or torch). The cloud a COLMAP scene starts from is its points3D.ply, in the
+    layout of storePly / fetchPly (fov3dgs/scene/dataset_readers.py:107-130: x y z nx ny nz float, red green blue uchar):
+    read it with read_ply_vertices and pass xyz and rgb / 255, as fetchPly does.
+      xyz      = points as float32
+      f_dc     = (rgb - 0.5) / C0 as [P,1,3], f_rest = zeros [P,(d+1)^2-1,3]
+      scaling  = log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))) repeated on the three axes
+      rotation = (1, 0, 0, 0), opacity = inverse_sigmoid(0.1), active SH degree 0 (of max_sh_degree = sh_degree)
+    The nearest-neighbour distances come from the HIP kernel (simple_knn), so `device` must be a ROCm GPU."""
+    from .simple_knn._C import distCUDA2
+    xyz = torch.tensor(np.asarray(points)).float().to(device)
+    fused_color = (torch.tensor(np.asarray(colors)).float().to(device) - 0.5) / 0.28209479177387814  # RGB2SH
+    P = xyz.shape[0]
+    features = torch.zeros((P, 3, (sh_degree + 1) ** 2), dtype=torch.float32, device=device)
+    features[:, :3, 0] = fused_color
+    dist2 = torch.clamp_min(distCUDA2(xyz), 0.0000001)
+    scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+    rots = torch.zeros((P, 4), device=device)
+    rots[:, 0] = 1
+    x = 0.1 * torch.ones((P, 1), dtype=torch.float, device=device)
+    opacities = torch.log(x / (1 - x))  # inverse_sigmoid
+    cloud = GaussianCloud(xyz, features[:, :, 0:1].transpose(1, 2).contiguous(), features[:, :, 1:].transpose(1, 2).contiguous(),
+                          scales, rots, opacities, sh_degree=sh_degree)
+    cloud.active_sh_degree = 0  # GaussianModel.__init__: training raises it with oneupSHdegree()
+    return cloud
+
+
 def compose_levels(ply_paths, sh_degree=3):
     """compose_models.compose(): ply_paths[0] is the finest model (all P Gaussians), ply_paths[i > 0] the level-i
     models written by save_ply_index (a subset, rows addressed by `index`).

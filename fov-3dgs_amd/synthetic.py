@@ -253,6 +253,41 @@ def scene_bicycle_scale(P=6_000_000, seed=1, device="cpu", scale_log_mean=math.l
     return GaussianCloud(xyz.contiguous(), f_dc, f_rest, scaling, rotation, opacity).to(device)
 
 
+def points_colmap_like(P, seed=4):
+    """A COLMAP-like sparse point cloud, f32[P,3] (the input of create_from_pcd): 60 % in dense anisotropic blobs of very
+    different sizes, 39 % on planar patches (walls, ground) with millimetre noise, 1 % far outliers out to 200 units."""
+    g = _gen(seed)
+    n_out = P // 100
+    n_plane = (39 * P) // 100
+    n_blob = P - n_out - n_plane
+    # blobs: 256 centres in a 20-unit box, log-uniform sizes 0.005..0.5, per-axis stretch
+    nb = 256
+    centres = (torch.rand(nb, 3, generator=g) * 2 - 1) * 10
+    sizes = torch.exp(torch.rand(nb, 1, generator=g) * math.log(100.0)) * 0.005
+    stretch = 0.3 + torch.rand(nb, 3, generator=g)
+    which = torch.randint(0, nb, (n_blob,), generator=g)
+    blobs = centres[which] + torch.randn(n_blob, 3, generator=g) * sizes[which] * stretch[which]
+    # planar patches: 32 random planes, square extents 1..6 units, noise 1 mm along the normal
+    npl = 32
+    origin = (torch.rand(npl, 3, generator=g) * 2 - 1) * 10
+    u = torch.randn(npl, 3, generator=g)
+    u = u / u.norm(dim=1, keepdim=True)
+    v = torch.randn(npl, 3, generator=g)
+    v = v - (v * u).sum(1, keepdim=True) * u
+    v = v / v.norm(dim=1, keepdim=True)
+    nrm = torch.cross(u, v, dim=1)
+    ext = 1 + 5 * torch.rand(npl, 1, generator=g)
+    which = torch.randint(0, npl, (n_plane,), generator=g)
+    a = (torch.rand(n_plane, 2, generator=g) * 2 - 1) * ext[which]
+    planes = origin[which] + a[:, :1] * u[which] + a[:, 1:] * v[which] + 0.001 * torch.randn(n_plane, 1, generator=g) * nrm[which]
+    # outliers: directions uniform on the sphere, radius 20..200
+    d = torch.randn(n_out, 3, generator=g)
+    d = d / d.norm(dim=1, keepdim=True)
+    outliers = d * (20 + 180 * torch.rand(n_out, 1, generator=g))
+    xyz = torch.cat([blobs, planes, outliers], 0)
+    return xyz[torch.randperm(P, generator=g)].to(torch.float32).contiguous()
+
+
 def scene_translucent(P=6_000_000, seed=1, device="cpu", opacity_logit=OPACITY_LOGIT_S6MT):
     """S-6M-T: the S-6M cloud with opacities drawn so that the blend CONSUMES its lists -- on S-6M (median alpha 0.73) every pixel
     saturates after 9 % (plain) to 20 % (foveated) of its tile's list, which no trained model does: the reference's loops run to

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FR_ABI_VERSION 9
+#define FR_ABI_VERSION 10
 
 /* rasterizer variants (the reference ships them as separate extensions; `cuda_type` strings of
  * fov3dgs/gaussian_wrapper.py:11-23) */
@@ -316,6 +316,18 @@ int fr_l1_ssim_forward(int32_t C, int32_t H, int32_t W, const float *img, const 
 int fr_l1_ssim_finish(int32_t C, int32_t H, int32_t W, const float *partials, float lambda_dssim, float *out3, void *stream);
 int fr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const float *target, const float *dmaps, float w_l1, float w_ssim,
 	const float *grad_scale, float *dL_dimg, void *stream);
+
+/* Mean squared distance of every point to its three nearest neighbours: simple-knn's distCUDA2, the initial scale of
+ * GaussianModel.create_from_pcd (replaces SimpleKNN::knn, fov3dgs/submodules/simple-knn/simple_knn.cu:185-220, as called by
+ * distCUDA2, spatial.cu:15-25). points: [P,3] fp32 device array; mean_dist2: [P] fp32, written in full:
+ *   mean_dist2[i] = ((b0 + b1) + b2) / 3.0f, b0 <= b1 <= b2 the three smallest d(i,j) = (dx*dx + dy*dy) + dz*dz over j != i
+ *   (dx = p_j.x - p_i.x, no fma), a missing neighbour counting as FLT_MAX (P = 3: about FLT_MAX / 3, P <= 2: +inf);
+ *   exact duplicates count at distance 0. The search is exact, so the result is one bit pattern, run after run.
+ *   A point with a non-finite coordinate gets NaN and is nobody's neighbour.
+ * workspace: fr_knn_workspace_bytes(P) bytes of device memory, 16-byte aligned (the library allocates nothing). Everything
+ * runs on `stream`, with no host synchronisation. P = 0 launches nothing. */
+size_t fr_knn_workspace_bytes(int32_t P);
+int fr_knn_mean_dist2(int32_t P, const float *points, float *mean_dist2, void *workspace, void *stream);
 
 /* Bytes fr_forward will request for the geometry / image workspaces (P, W, H dependent) and for the
  * binning workspace given a number of instances; lets a caller pre-size persistent buffers. */
