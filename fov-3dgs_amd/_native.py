@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (FOVRASTER_LIB: an experiment build of the library, tools/ab_build.sh -- never a different implementation: same ABI check)
 LIB_PATH = os.environ.get("FOVRASTER_LIB") or os.path.join(HERE, "libfovraster_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 VARIANT_ORIGINAL, VARIANT_PCHECK_OBB_SUM, VARIANT_PCHECK_OBB, VARIANT_FOV_PCHECK_OBB = 0, 1, 2, 3
 VARIANT_PCHECK_OBB_MAX, VARIANT_PCHECK_OBB_LWMC, VARIANT_NAIVE_FOV_PCHECK_OBB, VARIANT_MMFR_PCHECK_OBB = 4, 5, 6, 7
@@ -81,12 +81,29 @@ class BackwardArgs(C.Structure):
 RANGE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32)  # fr_backward_args.range_done(user, k, row_lo, row_hi)
 
 
+ADAM_MAX_TENSORS = 16
+ADAM_DENSE, ADAM_EXACT, ADAM_LAZY = 0, 1, 2
+
+
+class AdamTensor(C.Structure):
+    _fields_ = [
+        ("param", _FP), ("exp_avg", _FP), ("exp_avg_sq", _FP), ("grad", _FP), ("rows", _FP), ("row_map", _FP),
+        ("numel", C.c_int64), ("n_rows", C.c_int64), ("width", C.c_int32), ("mode", C.c_int32),
+        ("one_minus_beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta2", C.c_float),
+        ("bias_correction2_sqrt", C.c_float), ("eps", C.c_float), ("neg_step_size", C.c_float),
+    ]
+
+
+class AdamArgs(C.Structure):
+    _fields_ = [("num_tensors", C.c_int32), ("reserved", C.c_int32), ("tensors", AdamTensor * ADAM_MAX_TENSORS)]
+
+
 EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destroy", "fr_event_elapsed_ms", "fr_forward", "fr_backward", "fr_mark_visible", "fr_pack_geom", "fr_pack_colour", "fr_pack_cull", "fr_activate_forward", "fr_activate_backward", "fr_l1_ssim_blocks", "fr_l1_ssim_forward", "fr_l1_ssim_finish", "fr_l1_ssim_backward",
            "fr_geometry_bytes", "fr_image_bytes", "fr_binning_bytes", "fr_image_ranges",
            "fr_binning_point_list", "fr_image_final_T", "fr_image_n_contrib", "fr_image_tile_levels", "fr_geometry_records",
            "fr_geometry_vis_list", "fr_geometry_vis_count", "fr_geometry_walk_records", "fr_geometry_level_colours",
            "fr_geometry_level_ranges", "fr_forward_begin", "fr_forward_finish", "fr_forward_abandon", "fr_backward_prefill",
-           "fr_knn_workspace_bytes", "fr_knn_mean_dist2")
+           "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step")
 
 _lib = None
 
@@ -176,6 +193,8 @@ def load():
     lib.fr_knn_workspace_bytes.restype = C.c_size_t
     lib.fr_knn_mean_dist2.argtypes = [C.c_int32, _FP, _FP, C.c_void_p, C.c_void_p]
     lib.fr_knn_mean_dist2.restype = C.c_int
+    lib.fr_adam_step.argtypes = [C.POINTER(AdamArgs), C.c_void_p]
+    lib.fr_adam_step.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

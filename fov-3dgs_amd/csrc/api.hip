@@ -488,6 +488,34 @@ int fr_knn_mean_dist2(int32_t P, const float *points, float *mean_dist2, void *w
 	return launch_knn(P, points, mean_dist2, workspace, (hipStream_t)stream);
 }
 
+int fr_adam_step(const fr_adam_args *a, void *stream)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (a->num_tensors < 0 || a->num_tensors > FR_ADAM_MAX_TENSORS) { set_error("adam_step: %d tensors (at most %d)", a->num_tensors, FR_ADAM_MAX_TENSORS); return FR_ERR_INVALID; }
+	for (int k = 0; k < a->num_tensors; k++)
+	{
+		const fr_adam_tensor &t = a->tensors[k];
+		if (t.numel < 0 || t.n_rows < 0 || t.width <= 0 || t.mode < FR_ADAM_DENSE || t.mode > FR_ADAM_LAZY)
+		{ set_error("adam_step: tensor %d: bad sizes (numel=%lld n_rows=%lld width=%d mode=%d)", k, (long long)t.numel, (long long)t.n_rows, t.width, t.mode); return FR_ERR_INVALID; }
+		if (t.numel == 0) continue;
+		if (!t.param || !t.exp_avg || !t.exp_avg_sq) { set_error("adam_step: tensor %d: a state pointer is null", k); return FR_ERR_INVALID; }
+		if (t.mode == FR_ADAM_DENSE ? !t.grad : (t.n_rows > 0 && (!t.grad || !t.rows))) { set_error("adam_step: tensor %d: gradient pointer is null", k); return FR_ERR_INVALID; }
+		if (t.mode != FR_ADAM_DENSE && (t.numel % t.width || t.n_rows > t.numel / t.width))
+		{ set_error("adam_step: tensor %d: %lld rows of width %d do not fit %lld elements", k, (long long)t.n_rows, t.width, (long long)t.numel); return FR_ERR_INVALID; }
+	}
+	const fr_adam_tensor *first = nullptr; // the tensors that share the row map share what it is built from
+	for (int k = 0; k < a->num_tensors; k++)
+	{
+		const fr_adam_tensor &t = a->tensors[k];
+		if (t.mode != FR_ADAM_EXACT || !t.row_map || t.n_rows == 0 || t.numel == 0) continue;
+		if (t.n_rows > 0x7fffffff) { set_error("adam_step: tensor %d: too many rows for a row map", k); return FR_ERR_INVALID; }
+		if (!first) first = &t;
+		else if (t.row_map != first->row_map || t.rows != first->rows || t.n_rows != first->n_rows || t.numel / t.width != first->numel / first->width)
+		{ set_error("adam_step: tensor %d: one row map per call, shared only by tensors with the same rows", k); return FR_ERR_INVALID; }
+	}
+	return launch_adam(a, (hipStream_t)stream);
+}
+
 int fr_backward(const fr_backward_args *a)
 {
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }

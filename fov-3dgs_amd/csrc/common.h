@@ -467,6 +467,7 @@ int launch_activate_backward(int P, const float *rs, const float *rq, const floa
 	float *ds, float *dq, float *dop, hipStream_t stream);
 size_t knn_workspace_bytes(int P); // knn.hip
 int launch_knn(int P, const float *pts, float *out, void *ws, hipStream_t stream);
+int launch_adam(const fr_adam_args *a, hipStream_t stream); // optim.hip
 int launch_project(FwdCtx &c); // cull pass + the ordered compaction of its survivors
 int launch_bin(FwdCtx &c);    // projection of the cull pass's survivors, tile counts, colours, item rows
 int launch_tile_scan(FwdCtx &c);

@@ -824,6 +824,27 @@ def _mark_visible(positions, rs):
     return present
 
 
+def _keep_coalesced_flag(rows, leaves):
+    """autograd hands a sparse gradient to a leaf's .grad as a new tensor over the same indices and values, WITHOUT its
+    is_coalesced flag (AccumulateGrad rebuilds it), so optim.Adam would have to sort and sum rows that are already increasing
+    and unique -- with a device synchronisation -- on every step. At the end of the backward pass the flag is put back on
+    every .grad that still is exactly this call's rows (same memory, same count: a gradient accumulated into an existing .grad
+    has new indices and keeps whatever torch gave it)."""
+    ptr, shape = rows.data_ptr(), tuple(rows.shape)
+    leaves = [t for t in leaves if t is not None and t.requires_grad and t.is_leaf]
+    if not leaves:
+        return
+
+    def restore(rows=rows):  # (holds `rows`: its memory cannot be handed to another tensor before this has run)
+        for t in leaves:
+            g = t.grad
+            if g is not None and g.layout == torch.sparse_coo and not g.is_coalesced():
+                i = g._indices()
+                if i.data_ptr() == ptr and tuple(i.shape) == shape:
+                    g._coalesced_(True)
+    torch.autograd.Variable._execution_engine.queue_callback(restore)
+
+
 def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
     """Autograd function + module for the non-foveated variants. takes_loss_map: the
     …_loss_weighted_max_count extension has one extra input (`loss_map`, a [3,H,W] or [H,W] tensor)."""
@@ -837,7 +858,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             # does): the blend skips them and the call returns (color, radii) only
             # row_sparse (extension): backward returns the gradients of the [P, ...] inputs as SPARSE tensors (torch.sparse_coo, one
             # sparse dimension: the Gaussians this view touched) -- for leaf parameters (raw_activations + split SH: every input is
-            # one) optimised by a sparse-aware optimizer or summed with multiview.allreduce_gradients; no 1.5 GB of zero fills
+            # one) optimised by optim.Adam (sparse="exact" or "lazy") or summed with multiview.allreduce_gradients; no 1.5 GB of zero fills
             # raw_activations (extension): opacities / scales / rotations are the model's RAW parameters, the kernels apply
             # sigmoid / exp / normalize themselves and the backward pass returns the gradients w.r.t. the raw parameters
             # sh_rest (extension): the SH coefficients as the two tensors a model stores, sh = features_dc
@@ -945,6 +966,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
                 rows = visible_rows(variant_id, P, geomBuffer, ctx.num_candidates).unsqueeze(0)
                 res = tuple(None if g is None else torch.sparse_coo_tensor(rows, g, (P,) + tuple(g.shape[1:]), is_coalesced=True)
                             for g in res)
+                _keep_coalesced_flag(rows, (means3D, sh, opacities, scales, rotations, sh_rest))
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = res[:8]
             grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,

@@ -15,6 +15,8 @@
  *                         as called by RasterizeGaussiansBackwardCUDA (…/rasterize_points.cu:117-196)
  *   fr_mark_visible   <-  CudaRasterizer::Rasterizer::markVisible (…/rasterizer.h:24-29; rasterize_points.cu:198-217)
  *   fr_resize_fn      <-  the std::function<char*(size_t)> buffer callbacks (…/rasterize_points.cu:27-33)
+ *   fr_adam_step      <-  torch.optim.Adam(l, lr=0.0, eps=1e-15).step() (fov3dgs/scene/gaussian_model.py:289; not a native
+ *                         function of the reference: the last step of its training iteration, eff_finetune.py:147)
  *
  * Conventions: every pointer in the argument structs is a DEVICE pointer to fp32/int32 data laid
  * out exactly as the reference's tensors (row-major, contiguous) unless stated otherwise; NULL
@@ -39,7 +41,7 @@
 extern "C" {
 #endif
 
-#define FR_ABI_VERSION 10
+#define FR_ABI_VERSION 11
 
 /* rasterizer variants (the reference ships them as separate extensions; `cuda_type` strings of
  * fov3dgs/gaussian_wrapper.py:11-23) */
@@ -328,6 +330,50 @@ int fr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const
  * runs on `stream`, with no host synchronisation. P = 0 launches nothing. */
 size_t fr_knn_workspace_bytes(int32_t P);
 int fr_knn_mean_dist2(int32_t P, const float *points, float *mean_dist2, void *workspace, void *stream);
+
+/* The optimizer step of a training iteration: Adam over every parameter tensor of the model in one kernel launch (replaces
+ * torch.optim.Adam(l, lr=0.0, eps=1e-15), fov3dgs/scene/gaussian_model.py:289, as stepped by eff_finetune.py:147). No
+ * weight decay, amsgrad or maximize: the reference uses none. Per element, in torch's order of operations, every operation
+ * rounded once:
+ *   m = fma(one_minus_beta1, g - m, m);  v = fma(one_minus_beta2, g * g, v * beta2);   (the fusions of torch's GPU kernels)
+ *   p += neg_step_size * (m / (sqrt(v) / bias_correction2_sqrt + eps))
+ * with neg_step_size = -lr / (1 - beta1^t) and bias_correction2_sqrt = sqrt(1 - beta2^t) computed by the caller in double.
+ * Everything runs on `stream` with no host synchronisation and no allocation; the table travels in the kernel arguments. */
+#define FR_ADAM_MAX_TENSORS 16
+enum {
+	FR_ADAM_DENSE = 0, /* grad: [numel] */
+	FR_ADAM_EXACT = 1, /* row-sparse grad, a row without an entry has gradient zero: every row decays and moves (= dense Adam on to_dense()) */
+	FR_ADAM_LAZY = 2   /* row-sparse grad, only the listed rows of param / exp_avg / exp_avg_sq are read or written */
+};
+
+/* One parameter tensor of the step (replaces one entry of the param_groups of gaussian_model.py:289). All pointers are
+ * device pointers to contiguous data; param, exp_avg, exp_avg_sq: fp32 [numel], updated in place. Row-sparse modes: the
+ * tensor is [numel / width, width], grad holds the n_rows compact rows [n_rows, width] and rows [n_rows] their row numbers,
+ * strictly increasing (a coalesced torch.sparse_coo gradient with one sparse dimension). A row number outside
+ * [0, numel / width) is skipped, never dereferenced. */
+typedef struct fr_adam_tensor {
+	float *param, *exp_avg, *exp_avg_sq;
+	const float *grad;
+	const int64_t *rows; /* NULL in dense mode */
+	int32_t *row_map;    /* exact mode, optional: scratch int32 [numel / width] for the row -> compact position lookup (filled
+	                      * by the call, needs no initialisation; every tensor of a call that names it has the same rows, n_rows
+	                      * and row count). NULL = binary search in rows */
+	int64_t numel;
+	int64_t n_rows;      /* 0 in dense mode */
+	int32_t width;       /* elements per row (1 in dense mode) */
+	int32_t mode;        /* FR_ADAM_* */
+	float one_minus_beta1, beta2, one_minus_beta2;
+	float bias_correction2_sqrt, eps, neg_step_size;
+} fr_adam_tensor;
+
+/* The whole step (replaces optimizer.step() over the six groups of gaussian_model.py:289). */
+typedef struct fr_adam_args {
+	int32_t num_tensors; /* 0 .. FR_ADAM_MAX_TENSORS */
+	int32_t reserved;
+	fr_adam_tensor tensors[FR_ADAM_MAX_TENSORS];
+} fr_adam_args;
+
+int fr_adam_step(const fr_adam_args *args, void *stream);
 
 /* Bytes fr_forward will request for the geometry / image workspaces (P, W, H dependent) and for the
  * binning workspace given a number of instances; lets a caller pre-size persistent buffers. */
