@@ -98,12 +98,26 @@ class AdamArgs(C.Structure):
     _fields_ = [("num_tensors", C.c_int32), ("reserved", C.c_int32), ("tensors", AdamTensor * ADAM_MAX_TENSORS)]
 
 
+COMPACT_MAX_TENSORS = 32
+PRUNE_MAX_COMP_EFFICIENCY, PRUNE_CONTRIB = 0, 1
+
+
+class CompactTensor(C.Structure):
+    _fields_ = [("src", _FP), ("dst", _FP), ("row_words", C.c_int32), ("dst_rows", C.c_int32)]
+
+
+class CompactArgs(C.Structure):
+    _fields_ = [("P", C.c_int32), ("num_tensors", C.c_int32), ("invert", C.c_int32), ("reserved", C.c_int32),
+                ("mask", _FP), ("workspace", _FP), ("tensors", CompactTensor * COMPACT_MAX_TENSORS)]
+
+
 EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destroy", "fr_event_elapsed_ms", "fr_forward", "fr_backward", "fr_mark_visible", "fr_pack_geom", "fr_pack_colour", "fr_pack_cull", "fr_activate_forward", "fr_activate_backward", "fr_l1_ssim_blocks", "fr_l1_ssim_forward", "fr_l1_ssim_finish", "fr_l1_ssim_backward",
            "fr_geometry_bytes", "fr_image_bytes", "fr_binning_bytes", "fr_image_ranges",
            "fr_binning_point_list", "fr_image_final_T", "fr_image_n_contrib", "fr_image_tile_levels", "fr_geometry_records",
            "fr_geometry_vis_list", "fr_geometry_vis_count", "fr_geometry_walk_records", "fr_geometry_level_colours",
            "fr_geometry_level_ranges", "fr_forward_begin", "fr_forward_finish", "fr_forward_abandon", "fr_backward_prefill",
-           "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step")
+           "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step",
+           "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows")
 
 _lib = None
 
@@ -195,6 +209,16 @@ def load():
     lib.fr_knn_mean_dist2.restype = C.c_int
     lib.fr_adam_step.argtypes = [C.POINTER(AdamArgs), C.c_void_p]
     lib.fr_adam_step.restype = C.c_int
+    lib.fr_prune_workspace_bytes.argtypes = [C.c_int32]
+    lib.fr_prune_workspace_bytes.restype = C.c_size_t
+    lib.fr_prune_metric_max.argtypes = [C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_void_p]
+    lib.fr_prune_metric_max.restype = C.c_int
+    lib.fr_prune_select_lowest.argtypes = [C.c_int32, _FP, C.c_int64, _FP, C.c_void_p, C.c_void_p]
+    lib.fr_prune_select_lowest.restype = C.c_int
+    lib.fr_compact_plan.argtypes = [C.c_int32, _FP, C.c_int32, _FP, C.c_void_p, C.c_void_p]
+    lib.fr_compact_plan.restype = C.c_int
+    lib.fr_compact_rows.argtypes = [C.POINTER(CompactArgs), C.c_void_p]
+    lib.fr_compact_rows.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -516,6 +516,53 @@ int fr_adam_step(const fr_adam_args *a, void *stream)
 	return launch_adam(a, (hipStream_t)stream);
 }
 
+size_t fr_prune_workspace_bytes(int32_t P) { return prune_workspace_bytes(P); }
+
+int fr_prune_metric_max(int32_t P, int32_t kind, const float *contribs, const int32_t *counts, float *metrics, void *stream)
+{
+	if (P < 0) { set_error("prune_metric_max: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (kind != FR_PRUNE_MAX_COMP_EFFICIENCY && kind != FR_PRUNE_CONTRIB) { set_error("prune_metric_max: unknown kind %d", kind); return FR_ERR_INVALID; }
+	if (P > 0 && (!contribs || !metrics || (kind == FR_PRUNE_MAX_COMP_EFFICIENCY && !counts))) { set_error("prune_metric_max: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_prune_metric(P, kind, contribs, counts, metrics, (hipStream_t)stream);
+}
+
+int fr_prune_select_lowest(int32_t P, const float *metrics, int64_t k, uint8_t *mask, void *workspace, void *stream)
+{
+	if (P < 0) { set_error("prune_select_lowest: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (k < 0 || k > P) { set_error("prune_select_lowest: k=%lld is not in 0..P=%d", (long long)k, P); return FR_ERR_INVALID; }
+	if (P > 0 && (!metrics || !mask || !workspace)) { set_error("prune_select_lowest: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	if ((uintptr_t)workspace % 16) { set_error("prune workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	return launch_prune_select(P, metrics, k, mask, workspace, (hipStream_t)stream);
+}
+
+int fr_compact_plan(int32_t P, const uint8_t *mask, int32_t invert, int32_t *count_out, void *workspace, void *stream)
+{
+	if (P < 0) { set_error("compact_plan: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (P > 0 && (!mask || !count_out || !workspace)) { set_error("compact_plan: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK; // (nothing launched: *count_out is not written)
+	if ((uintptr_t)workspace % 16) { set_error("prune workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	return launch_compact_plan(P, mask, invert, count_out, workspace, (hipStream_t)stream);
+}
+
+int fr_compact_rows(const fr_compact_args *a, void *stream)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (a->P < 0) { set_error("compact_rows: bad size P=%d", a->P); return FR_ERR_INVALID; }
+	if (a->num_tensors < 0 || a->num_tensors > FR_COMPACT_MAX_TENSORS) { set_error("compact_rows: %d tensors (at most %d)", a->num_tensors, FR_COMPACT_MAX_TENSORS); return FR_ERR_INVALID; }
+	if (a->P > 0 && (!a->mask || !a->workspace)) { set_error("compact_rows: mask or workspace is null"); return FR_ERR_INVALID; }
+	for (int k = 0; k < a->num_tensors; k++)
+	{
+		const fr_compact_tensor &t = a->tensors[k];
+		if (t.row_words < 0 || t.dst_rows < 0 || t.dst_rows > a->P) { set_error("compact_rows: tensor %d: bad sizes (row_words=%d dst_rows=%d P=%d)", k, t.row_words, t.dst_rows, a->P); return FR_ERR_INVALID; }
+		if (a->P > 0 && t.row_words > 0 && t.dst_rows > 0 && (!t.src || !t.dst)) { set_error("compact_rows: tensor %d: a data pointer is null", k); return FR_ERR_INVALID; }
+	}
+	if (a->P == 0 || a->num_tensors == 0) return FR_OK;
+	if ((uintptr_t)a->workspace % 16) { set_error("prune workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	return launch_compact_rows(a, (hipStream_t)stream);
+}
+
 int fr_backward(const fr_backward_args *a)
 {
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }

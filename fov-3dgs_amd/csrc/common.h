@@ -468,6 +468,11 @@ int launch_activate_backward(int P, const float *rs, const float *rq, const floa
 size_t knn_workspace_bytes(int P); // knn.hip
 int launch_knn(int P, const float *pts, float *out, void *ws, hipStream_t stream);
 int launch_adam(const fr_adam_args *a, hipStream_t stream); // optim.hip
+size_t prune_workspace_bytes(int P); // prune.hip
+int launch_prune_metric(int P, int kind, const float *contribs, const int32_t *counts, float *metrics, hipStream_t stream);
+int launch_prune_select(int P, const float *metrics, int64_t k, uint8_t *mask, void *ws, hipStream_t stream);
+int launch_compact_plan(int P, const uint8_t *mask, int invert, int32_t *count_out, void *ws, hipStream_t stream);
+int launch_compact_rows(const fr_compact_args *a, hipStream_t stream);
 int launch_project(FwdCtx &c); // cull pass + the ordered compaction of its survivors
 int launch_bin(FwdCtx &c);    // projection of the cull pass's survivors, tile counts, colours, item rows
 int launch_tile_scan(FwdCtx &c);

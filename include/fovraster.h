@@ -375,6 +375,57 @@ typedef struct fr_adam_args {
 
 int fr_adam_step(const fr_adam_args *args, void *stream);
 
+/* The pruning step of the Fov-3DGS loop (replaces metric_pruning, fov3dgs/prune.py:71-110 -- the same loop in
+ * metric_mask_learn.py:72-111 -- and GaussianModel._prune_optimizer / prune_points, fov3dgs/scene/gaussian_model.py:624-664).
+ * Everything runs on `stream` with no host synchronisation and no allocation, and every output is one bit pattern, run after
+ * run. workspace: fr_prune_workspace_bytes(P) bytes of device memory, 16-byte aligned, shared by the select and the
+ * compaction (a plan stays valid until the next plan or select on the same workspace). P = 0 launches nothing. */
+#define FR_COMPACT_MAX_TENSORS 32
+enum {
+	FR_PRUNE_MAX_COMP_EFFICIENCY = 0, /* cur = counts < 1 ? 0 : contribs / ((float)counts + 1e-7f)          (prune.py:79-86) */
+	FR_PRUNE_CONTRIB = 1              /* cur = contribs: the reference's "surface" and "max_contrib"; counts unused (prune.py:87-98) */
+};
+size_t fr_prune_workspace_bytes(int32_t P);
+
+/* One view's update of the metric, in place (replaces prune.py:82-86 / :90-92 / :95-98):
+ *   metrics[i] = metrics[i] < cur ? cur : metrics[i]        (a NaN cur leaves the old value)
+ * contribs: [P] fp32 and counts: [P] int32 as the rasterizer returns them; every operation is rounded once in fp32, the
+ * division correctly: the result equals the torch expression bit for bit. */
+int fr_prune_metric_max(int32_t P, int32_t kind, const float *contribs, const int32_t *counts, float *metrics, void *stream);
+
+/* The rows to prune (replaces the torch.sort, the index slice and the mask scatter of prune.py:101-107): mask [P] bytes,
+ * written in full, with exactly k ones: the k smallest rows under the total order (key(m), index), where for the bit
+ * pattern b of m  key = 0xFFFFFFFF (NaN), 0x80000000 (+0 or -0), ~b (sign bit set), b | 0x80000000 (otherwise) -- the
+ * order of torch.sort(descending=False, stable=True). Inside a run of equal metrics the lowest indices go first. */
+int fr_prune_select_lowest(int32_t P, const float *metrics, int64_t k, uint8_t *mask, void *workspace, void *stream);
+
+/* Row compaction (replaces the 21 tensor[valid_points_mask] gathers of gaussian_model.py:629-664), in two calls so that the
+ * caller can allocate between them. A row is kept when its mask byte is non-zero (invert = 0) or zero (invert != 0).
+ *   plan: each workgroup's first destination row, into the workspace, and *count_out (a DEVICE int32) = the kept rows
+ *         (P = 0 launches nothing and leaves *count_out unwritten).
+ *   rows: out[j] = src[i_j] bitwise for the kept rows i_0 < i_1 < ..., for every tensor of the table in ONE launch; mask and
+ *         invert are those of the plan. A row is row_words 4-byte words (0: the tensor is skipped); a destination row
+ *         >= dst_rows is never written. */
+typedef struct fr_compact_tensor {
+	const void *src;   /* [P, row_words] words, contiguous */
+	void *dst;         /* [dst_rows, row_words] words, contiguous; may be NULL when dst_rows or row_words is 0 */
+	int32_t row_words;
+	int32_t dst_rows;
+} fr_compact_tensor;
+
+typedef struct fr_compact_args {
+	int32_t P;
+	int32_t num_tensors; /* 0 .. FR_COMPACT_MAX_TENSORS */
+	int32_t invert;
+	int32_t reserved;
+	const uint8_t *mask; /* [P] */
+	void *workspace;     /* as given to fr_compact_plan */
+	fr_compact_tensor tensors[FR_COMPACT_MAX_TENSORS];
+} fr_compact_args;
+
+int fr_compact_plan(int32_t P, const uint8_t *mask, int32_t invert, int32_t *count_out, void *workspace, void *stream);
+int fr_compact_rows(const fr_compact_args *args, void *stream);
+
 /* Bytes fr_forward will request for the geometry / image workspaces (P, W, H dependent) and for the
  * binning workspace given a number of instances; lets a caller pre-size persistent buffers. */
 size_t fr_geometry_bytes(int32_t variant, int32_t P);
