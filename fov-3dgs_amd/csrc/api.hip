@@ -335,7 +335,7 @@ int fr_forward_finish(fr_frame *f)
 	const int64_t early_cap = (same_kind && !a->debug) ? gs.capacity : 0;
 	if (early_cap > 0) early_bin = a->binning_resize(a->resize_user[1], carve_bin(early_cap, nullptr, c.T).bytes);
 
-	uint32_t totals[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, candidates = 0, region_overflow = 0;
+	uint32_t totals[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, candidates = 0, region_overflow = 0;
 	uint32_t *const pinned = f->pin ? f->pin->host : nullptr;
 	if (!pinned)
 	{
@@ -360,6 +360,7 @@ int fr_forward_finish(fr_frame *f)
 			}
 		for (int i = 0; i < 4; i++) totals[i] = v[i];
 		totals[5] = v[5]; totals[6] = v[6]; totals[7] = v[7]; candidates = v[8]; region_overflow = v[9];
+		totals[8] = v[10]; totals[9] = v[11]; // (the device's totals[8], [9]: words 8 and 9 of the block were taken)
 	}
 	c.regions_ok = region_overflow == 0 ? 1 : 0;
 	f->totals_read = true;
@@ -373,6 +374,7 @@ int fr_forward_finish(fr_frame *f)
 	a->num_candidates = (int32_t)candidates;
 	c.heavy4 = (int)totals[2]; c.heavy2 = (int)totals[3];
 	c.n_items = (int)totals[5]; c.heavy8 = (int)totals[6];
+	c.heavy16 = (int)totals[8]; c.heavy32 = (int)totals[9];
 	// what the next frame of this kind will ask for: a quarter of headroom over the largest frame seen
 	const int64_t want = (int64_t)totals[0] + (int64_t)totals[0] / 4 + 65536;
 	if (!same_kind) { gs.variant = a->variant; gs.P = a->P; gs.W = a->W; gs.H = a->H; gs.capacity = 0; }

@@ -25,41 +25,55 @@ __global__ void __launch_bounds__(FR_TILE_SCAN_THREADS) k_tile_scan(const TileSc
 	else tile_scan_atomics<FR_TILE_SCAN_THREADS>(ts);
 }
 
-// The two classes of short lists, one workgroup per list: the lists of 512..2047 entries (the tile scan's bins 10 and 11:
-// tile_order[h4 .. h4 + mid), h4 = totals[2], mid = totals[3]) when !SHORTEST, the lists of <= 511 entries (the rest of
-// tile_order, empty tiles included) when SHORTEST.
-template <int THREADS, int ITEMS, bool SHORTEST>
-__global__ void __launch_bounds__(THREADS) k_tile_msort(const uint2 *ranges, const uint32_t *tile_order, uint64_t *entries,
+// The two classes of short lists in one launch of 256 threads (totals[2] = h4 lists of >= 2048 entries lead tile_order, totals[3] =
+// mid lists of 512..2047 entries follow -- the tile scan's bins 10 and 11 --, the rest has <= 511 entries, empty tiles included):
+// workgroups [0, mid) sort one list of the middle class each; the workgroups behind them sort four of the shortest lists each, one
+// per wave, every wave for itself (GROUPS = 4 in tile_sort.h: no workgroup barrier on that side of the branch, which is
+// uniform per workgroup). The grid is exactly mid + ceil((T - h4 - mid) / 4).
+#define FR_SORT_SHORT_THREADS 256
+#define FR_SORT_SHORT_LDS_KEYS 2304 // 256 x 8 keys + a spare slot per thread = 4 x (64 x 8 keys + a spare slot per lane)
+__global__ void __launch_bounds__(FR_SORT_SHORT_THREADS) k_tile_msort(const uint2 *ranges, const uint32_t *tile_order, uint64_t *entries,
 	uint32_t *point_list, int T, const uint32_t *totals, SpecLimits lim)
 {
 	extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
 	if (!frame_fits(totals, lim)) return;
-	const uint32_t lo = totals[2] + (SHORTEST ? totals[3] : 0u), hi = SHORTEST ? (uint32_t)T : totals[2] + totals[3];
-	for (uint32_t b = lo + blockIdx.x; b < hi; b += gridDim.x)
+	const uint32_t h4 = totals[2], mid = totals[3];
+	if (blockIdx.x < mid)
 	{
-		const uint2 rg = ranges[tile_order[b]];
-		if (rg.y != rg.x) msort_list<THREADS, ITEMS, false>(rg, entries, point_list, sk);
-		__syncthreads(); // the next list reuses the LDS keys
+		msort_list<FR_SORT_SHORT_THREADS, 8, false>(ranges[tile_order[h4 + blockIdx.x]], entries, point_list, sk);
+		return;
 	}
+	constexpr int WAVES = FR_SORT_SHORT_THREADS / 64;
+	const uint32_t wave = threadIdx.x >> 6;
+	const uint32_t b = h4 + mid + (blockIdx.x - mid) * WAVES + wave;
+	if (b >= (uint32_t)T) return;
+	const uint2 rg = ranges[tile_order[b]];
+	if (rg.y != rg.x) msort_list<64, 8, false, WAVES>(rg, entries, point_list, sk + wave * (FR_SORT_SHORT_LDS_KEYS / WAVES));
 }
 
-// The classes of longer lists, each sorted WHOLE in LDS by one workgroup: tile_order[totals[lo_word] .. totals[hi_word]) -- the
-// tile scan lays the tiles out longest first and counts the lists with >= 2048 / 4096 / 8192 / 16384 entries (totals[2], [6],
-// [8], [9]), so a class is a slice of tile_order. The grid is normally one workgroup per list (the hardware's placement
-// of fresh workgroups is the load balancer); the loop covers a grid sized from a bound that came out too small.
-template <int THREADS, int ITEMS>
+// The lists of 2048 entries and more that fit one workgroup's LDS, each sorted WHOLE by one workgroup: the tile scan lays the tiles
+// out longest first and counts the lists with >= 2048 / 4096 / 8192 / 16384 entries (totals[2], [6], [8], [9]), so workgroup b takes
+// tile_order[totals[lo_word] + b] and a launch covers tile_order[totals[lo_word] .. totals[hi_word]). <512, 8>: every list of
+// 2048..8191 entries in ONE launch -- the workgroup picks the capacity that fits ITS list, 512 x 8 or 512 x 16 keys (the branch is
+// uniform per workgroup), so a list of 2100 entries does not pay for the scan over the 16 384 buckets of an 8192-key sort; the
+// launch's dynamic LDS is what the frame's longest list of the range needs (launch_tile_sort). <1024, 16>: the lists of
+// 8192..16383 entries. One workgroup per list, the grid is exactly the number of lists (the hardware's placement of fresh
+// workgroups is the load balancer).
+template <int THREADS, int LO_ITEMS>
 __global__ void __launch_bounds__(THREADS, 4) k_tile_msort_direct(const uint2 *ranges, const uint32_t *tile_order, uint64_t *entries,
 	uint32_t *point_list, const uint32_t *totals, SpecLimits lim, int lo_word, int hi_word)
 {
 	extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
 	if (!frame_fits(totals, lim)) return;
-	const uint32_t lo = totals[lo_word], hi = totals[hi_word];
-	for (uint32_t b = lo + blockIdx.x; b < hi; b += gridDim.x)
-	{
-		msort_list<THREADS, ITEMS, false>(ranges[tile_order[b]], entries, point_list, sk);
-		__syncthreads(); // the next list reuses the LDS keys
-	}
+	// (no loop over lists: what does not depend on the list would be hoisted out of it for both capacities at once, and spills)
+	const uint32_t b = totals[lo_word] + blockIdx.x;
+	if (b >= totals[hi_word]) return;
+	const uint2 rg = ranges[tile_order[b]];
+	if (LO_ITEMS < 16 && rg.y - rg.x <= (uint32_t)(THREADS * LO_ITEMS)) msort_list<THREADS, LO_ITEMS, false>(rg, entries, point_list, sk);
+	else msort_list<THREADS, 16, false>(rg, entries, point_list, sk);
 }
+// LDS bytes of a whole-list sort of THREADS x ITEMS keys: the keys + one spare slot per thread (sk_slot)
+constexpr int sort_lds_bytes(const int threads, const int items) { return (threads * items + threads) * (int)sizeof(uint64_t); }
 
 // The chunks of the split long lists (k_split_long): chunks[0 .. totals[4]), any length; one workgroup per chunk (the grid is
 // the bound FR_SORT_MAX_CHUNKS of the workspace's capacity; the loop is a safety net).
@@ -113,8 +127,8 @@ int launch_tile_scan(FwdCtx &c)
 
 // Helper streams of the calling host thread, one pair per (device, launch stream), created on first use: two frames in flight on
 // two launch streams must not share them (frame n + 1's fills would queue behind frame n's colours). The size classes of the
-// per-tile sort are independent kernels; the classes with long lists hold a handful of tiles that each keep one CU busy
-// for 50-80 us, so the (many) short lists are sorted meanwhile on the helper stream `s` (event fork / join); `s2` carries a
+// per-tile sort are independent kernels, so with helper streams on the (many) short lists are sorted on the helper stream `s`
+// (event fork / join) beside the long ones; `s2` carries a
 // frame's fills and its colour kernel (fr_forward_begin / _finish), `s` also the backward pass's gradient fills.
 AuxStream *aux_stream(hipStream_t main)
 {
@@ -148,12 +162,15 @@ AuxStream *aux_stream(hipStream_t main)
 	return a.ok ? &a : nullptr;
 }
 
-// Stage "tile_sort": one kernel per size class, every list sorted whole in LDS by one workgroup (sort_keys_lds, tile_sort.h):
-//   <= 512 entries: one wave;  513..2047: 256 threads;  2048..4095: 512 threads;  4096..8191: 512 threads x 16 keys;
-//   8192..16383: 1024 threads x 16 keys (139 KiB of LDS);  longer: regrouped by depth into chunks first (k_split_long).
-// The classes are independent: the three of the long lists run on the launch stream, the two of the short lists meanwhile on
-// the helper stream (event fork / join). Every kernel finds its lists from the tile scan's class counts in device memory (the
-// grids come from the host's copy of them) and loops if its grid came out too small.
+// Stage "tile_sort": every list sorted whole in LDS by one workgroup (sort_keys_lds, tile_sort.h), in two or three launches:
+//   k_tile_msort_direct<1024, 16>: the lists of 8192..16383 entries, when the frame has any (139 KiB of LDS: a CU each);
+//   k_tile_msort_direct<512, 8>: the lists of 2048..8191 entries, 8 or 16 keys per thread chosen per workgroup;
+//   k_tile_msort: 512..2047: 256 threads;  <= 511 entries: one wave, four lists per workgroup;
+//   longer lists: regrouped by depth into chunks first (k_split_long + k_tile_msort_chunks, two more launches).
+// The launches are independent of each other: with helper streams on (training frames) the short lists are sorted meanwhile on
+// the helper stream (event fork / join). Every kernel finds its lists from the tile scan's class counts in device memory; the
+// grids and the LDS of the 2048..8191 launch come from the host's copy of them. Why the lists of 8192 and more keep a launch of
+// their own, and the measurements: DESIGN.md section 4 item 5 and its appendix ("Sort launches").
 int launch_tile_sort(FwdCtx &c)
 {
 	const uint2 *rg = c.img.ranges;
@@ -161,13 +178,9 @@ int launch_tile_sort(FwdCtx &c)
 	uint32_t *totals = c.img.totals;
 	const SpecLimits lim = { (uint32_t)c.capacity, (uint32_t)c.items_cap };
 	static const bool serial = getenv("FR_SERIAL_SORT") != nullptr;
-	const int h4 = c.heavy4, h8 = c.heavy8;
-	const int longest = c.a->max_tile_instances;
+	const int h4 = c.heavy4, h8 = c.heavy8, h16 = c.heavy16, h32 = c.heavy32;
 	// long lists exist: the short ones are sorted meanwhile on the helper stream
 	AuxStream *ax = (h4 > 0 && !serial && !c.a->debug && !c.a->no_helper_streams) ? aux_stream(c.stream) : nullptr;
-	// (measured on the S-6M frames, stage time: this split 88 us; the 2048..4095 class on the helper stream too 94; on a third
-	// stream 96; the 8192..16383 class -- a handful of workgroups that need a whole CU's LDS each -- on a third stream 95: the
-	// stage is bound by the sum of the work, not by a chain)
 	hipStream_t small = c.stream;
 	if (ax)
 	{
@@ -175,44 +188,38 @@ int launch_tile_sort(FwdCtx &c)
 		(void)hipStreamWaitEvent(ax->s, ax->fork, 0);
 		small = ax->s;
 	}
-	if (longest >= FR_SORT_SPLIT_MIN)
+	if (h32 > 0)
 	{
 		static const hipError_t lds_ok = hipFuncSetAttribute((const void *)k_split_long, hipFuncAttributeMaxDynamicSharedMemorySize, FR_SPLIT_LDS_KEYS * (int)sizeof(uint64_t));
 		if (lds_ok != hipSuccess) { set_error("hipFuncSetAttribute(k_split_long): %s", hipGetErrorString(lds_ok)); return FR_ERR_HIP; }
-		const int nsplit = h8 < 256 ? (h8 > 0 ? h8 : 1) : 256; // (how many lists are that long is only known on the device)
-		hipLaunchKernelGGL(k_split_long, dim3(nsplit), dim3(FR_SPLIT_THREADS), FR_SPLIT_LDS_KEYS * sizeof(uint64_t), c.stream, rg, ord, c.bin.entries,
+		hipLaunchKernelGGL(k_split_long, dim3(h32 < 256 ? h32 : 256), dim3(FR_SPLIT_THREADS), FR_SPLIT_LDS_KEYS * sizeof(uint64_t), c.stream, rg, ord, c.bin.entries,
 			c.bin.entries2, c.bin.chunks, totals, lim);
 		const size_t max_chunks = FR_SORT_MAX_CHUNKS(c.capacity);
 		hipLaunchKernelGGL((k_tile_msort_chunks<256, 8>), dim3((unsigned)max_chunks), dim3(256), 2304 * sizeof(uint64_t), c.stream,
 			c.bin.chunks, c.bin.entries2, c.bin.point_list, totals, lim);
 	}
-	if (longest >= 8192 && h8 > 0)
+	if (h16 - h32 > 0)
 	{
-		constexpr int lds = (16384 + 1024) * (int)sizeof(uint64_t);
+		constexpr int lds = sort_lds_bytes(1024, 16);
 		static const hipError_t lds_ok = hipFuncSetAttribute((const void *)k_tile_msort_direct<1024, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 		if (lds_ok != hipSuccess) { set_error("hipFuncSetAttribute(k_tile_msort_direct<1024, 16>): %s", hipGetErrorString(lds_ok)); return FR_ERR_HIP; }
-		hipLaunchKernelGGL((k_tile_msort_direct<1024, 16>), dim3(h8 < 256 ? h8 : 256), dim3(1024), lds, c.stream, rg, ord, c.bin.entries, c.bin.point_list,
-			totals, lim, 9, 8);
+		hipLaunchKernelGGL((k_tile_msort_direct<1024, 16>), dim3(h16 - h32), dim3(1024), lds, c.stream, rg, ord, c.bin.entries, c.bin.point_list, totals, lim, 9, 8);
 	}
-	if (longest >= 4096 && h8 > 0)
+	if (h4 - h16 > 0)
 	{
-		constexpr int lds = (8192 + 512) * (int)sizeof(uint64_t);
-		static const hipError_t lds_ok = hipFuncSetAttribute((const void *)k_tile_msort_direct<512, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-		if (lds_ok != hipSuccess) { set_error("hipFuncSetAttribute(k_tile_msort_direct<512, 16>): %s", hipGetErrorString(lds_ok)); return FR_ERR_HIP; }
-		hipLaunchKernelGGL((k_tile_msort_direct<512, 16>), dim3(h8), dim3(512), lds, c.stream, rg, ord, c.bin.entries, c.bin.point_list, totals, lim, 8, 6);
+		static const hipError_t lds_ok = hipFuncSetAttribute((const void *)k_tile_msort_direct<512, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, sort_lds_bytes(512, 16));
+		if (lds_ok != hipSuccess) { set_error("hipFuncSetAttribute(k_tile_msort_direct<512, 8>): %s", hipGetErrorString(lds_ok)); return FR_ERR_HIP; }
+		// the LDS of the launch: 70 KiB when a list of 4096..8191 entries exists, 37 KiB otherwise (the kernel's branch on a list's
+		// length never picks a capacity above it: the counts are the ones the kernel reads)
+		hipLaunchKernelGGL((k_tile_msort_direct<512, 8>), dim3(h4 - h16), dim3(512), sort_lds_bytes(512, h8 - h16 > 0 ? 16 : 8), c.stream, rg, ord,
+			c.bin.entries, c.bin.point_list, totals, lim, 8, 2);
 	}
-	if (h4 - h8 > 0)
-		hipLaunchKernelGGL((k_tile_msort_direct<512, 8>), dim3(h4 - h8), dim3(512), 4608 * sizeof(uint64_t), c.stream, rg, ord, c.bin.entries,
-			c.bin.point_list, totals, lim, 6, 2);
-	// (one workgroup per list of the class: a grid over all T tiles started 16 000 workgroups per frame only to find out that
-	// the list belongs to another kernel)
+	// (one workgroup per list or per four lists of the class: a grid over all T tiles started 16 000 workgroups per frame only to
+	// find out that the list belongs to another kernel)
 	const int nmid = c.heavy2, nshort = c.T - c.heavy4 - c.heavy2;
-	if (nmid > 0)
-		hipLaunchKernelGGL((k_tile_msort<256, 8, false>), dim3(nmid), dim3(256), 2304 * sizeof(uint64_t), small, rg, ord, c.bin.entries, c.bin.point_list,
-			c.T, totals, lim);
-	if (nshort > 0)
-		hipLaunchKernelGGL((k_tile_msort<64, 8, true>), dim3(nshort), dim3(64), 576 * sizeof(uint64_t), small, rg, ord, c.bin.entries, c.bin.point_list,
-			c.T, totals, lim);
+	if (nmid + nshort > 0)
+		hipLaunchKernelGGL(k_tile_msort, dim3(nmid + (nshort + 3) / 4), dim3(FR_SORT_SHORT_THREADS), FR_SORT_SHORT_LDS_KEYS * sizeof(uint64_t), small,
+			rg, ord, c.bin.entries, c.bin.point_list, c.T, totals, lim);
 	if (ax)
 	{
 		(void)hipEventRecord(ax->join, ax->s);

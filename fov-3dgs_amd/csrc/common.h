@@ -440,6 +440,7 @@ struct FwdCtx {
 	int regions, region_rx, wcap; // region-major emission (launch_bin decides): regions of the tile grid (0 = off), regions per row, entries of a workgroup's segment
 	int heavy4, heavy2; // tiles with >= 2048 / 512..2047 instances (leading entries of tile_order)
 	int heavy8;         // tiles with >= 4096 instances
+	int heavy16, heavy32; // ... >= 8192, >= 16384 (FR_SORT_SPLIT_MIN)
 	int n_items;        // entries of ImageWS::render_items
 	int proj_waves, proj_cpw; // the cull pass's grid in waves and the consecutive chunks each wave took
 	int64_t capacity;   // instances the binning workspace was carved for

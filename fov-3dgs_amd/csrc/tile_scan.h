@@ -60,6 +60,7 @@ __device__ __forceinline__ void publish_totals(const TileScanArgs &ts, const uin
 		// slab_ctr[5]: a binning workgroup's region list did not fit its segment (raised with device-scope atomics by workgroups that may
 		// sit on another XCD: read from the memory side)
 		totals_host[9] = __hip_atomic_load(ts.prefilter_flag + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		totals_host[10] = h16; totals_host[11] = h32; // (the host sizes the long-list sort's grids and LDS from them)
 		__threadfence_system();
 		__hip_atomic_store(&totals_host[4], ts.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 	}

@@ -95,6 +95,27 @@ template <int ITEMS> __device__ __forceinline__ int sk_slot(const int i) { retur
 // in registers (odd-even transposition network), then log2(nact / ITEMS) merge passes follow: a thread
 // finds its ITEMS-long slice of the merged output by a merge-path binary search and merges it
 // sequentially out of LDS into registers; results are written back in place after a barrier.
+// GROUPS: how many lists the workgroup sorts side by side, each by THREADS of its threads. 1: the whole workgroup sorts one list.
+// More: THREADS is 64, every wave sorts a list of its own with its own slice of LDS and its own entry of the little static
+// arrays, and what orders the wave's LDS accesses is a fence (a wave's LDS operations complete in order): no workgroup barrier,
+// so the waves need not take the same number of rounds.
+template <int THREADS, int GROUPS>
+__device__ __forceinline__ int group_tid()
+{
+	static_assert(GROUPS == 1 || THREADS == 64, "lists side by side in one workgroup: one wave each");
+	return GROUPS == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 63u);
+}
+template <int GROUPS>
+__device__ __forceinline__ void group_sync()
+{
+	if (GROUPS == 1) __syncthreads();
+	else
+	{
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+	}
+}
 template <int THREADS, int ITEMS>
 __device__ __forceinline__ int msort_active(const int n)
 {
@@ -102,10 +123,10 @@ __device__ __forceinline__ int msort_active(const int n)
 	while (runs * ITEMS < n) runs <<= 1;
 	return runs * ITEMS;
 }
-template <int THREADS, int ITEMS>
+template <int THREADS, int ITEMS, int GROUPS = 1>
 __device__ __forceinline__ void msort_lds(uint64_t *sk, const int nact)
 {
-	const int tid = threadIdx.x;
+	const int tid = group_tid<THREADS, GROUPS>();
 #define SK(i) sk[sk_slot<ITEMS>(i)]
 	const bool act = tid * ITEMS < nact;
 	uint64_t k[ITEMS];
@@ -118,7 +139,7 @@ __device__ __forceinline__ void msort_lds(uint64_t *sk, const int nact)
 #pragma unroll
 		for (int i = 0; i < ITEMS; i++) SK(o + i) = k[i];
 	}
-	__syncthreads();
+	group_sync<GROUPS>();
 	for (int L = ITEMS; L < nact; L <<= 1)
 	{
 		if (act)
@@ -147,13 +168,13 @@ __device__ __forceinline__ void msort_lds(uint64_t *sk, const int nact)
 #undef A
 #undef B
 		}
-		__syncthreads();
+		group_sync<GROUPS>();
 		if (act)
 		{
 #pragma unroll
 			for (int t = 0; t < ITEMS; t++) SK(o + t) = k[t];
 		}
-		__syncthreads();
+		group_sync<GROUPS>();
 	}
 #undef SK
 }
@@ -172,13 +193,15 @@ __device__ __forceinline__ void msort_lds(uint64_t *sk, const int nact)
 #ifndef FR_BUCKET_SORT_MAX_OCC
 #define FR_BUCKET_SORT_MAX_OCC 40
 #endif
-template <int THREADS, int ITEMS>
+template <int THREADS, int ITEMS, int GROUPS = 1>
 __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], const int n, uint64_t *sk)
 {
 	constexpr int CAP = THREADS * ITEMS, NB = 2 * CAP, NW = THREADS / 64, PER = NB / THREADS;
 	uint32_t *const hist = (uint32_t *)sk; // NB words = CAP key slots
-	__shared__ uint32_t s_min[NW], s_max[NW], s_wave[NW], s_occ[NW];
-	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	__shared__ uint32_t s_all[4][GROUPS * NW];
+	const int tid = group_tid<THREADS, GROUPS>(), lane = tid & 63, wid = tid >> 6;
+	const int grp = GROUPS == 1 ? 0 : (int)(threadIdx.x >> 6) * NW;
+	uint32_t *const s_min = s_all[0] + grp, *const s_max = s_all[1] + grp, *const s_wave = s_all[2] + grp, *const s_occ = s_all[3] + grp;
 	uint32_t dmin = 0xffffffffu, dmax = 0u;
 #pragma unroll
 	for (int t = 0; t < ITEMS; t++)
@@ -187,7 +210,7 @@ __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], cons
 	for (int off = 32; off > 0; off >>= 1) { dmin = min(dmin, (uint32_t)__shfl_xor((int)dmin, off)); dmax = max(dmax, (uint32_t)__shfl_xor((int)dmax, off)); }
 	if (lane == 0) { s_min[wid] = dmin; s_max[wid] = dmax; }
 	for (int b = tid; b < NB; b += THREADS) hist[b] = 0;
-	__syncthreads();
+	group_sync<GROUPS>();
 #pragma unroll
 	for (int w = 0; w < NW; w++) { dmin = min(dmin, s_min[w]); dmax = max(dmax, s_max[w]); }
 	const float inv = (float)NB / ((float)(dmax - dmin) + 1.0f);
@@ -196,7 +219,7 @@ __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], cons
 #pragma unroll
 	for (int t = 0; t < ITEMS; t++)
 		if (tid + t * THREADS < n) rk[t] = atomicAdd(&hist[bucket_of(key[t])], 1u);
-	__syncthreads();
+	group_sync<GROUPS>();
 	// exclusive scan of the bucket counts (PER consecutive buckets per thread, read twice: no registers held), fullest bucket
 	uint32_t sum = 0, occ = 0;
 #pragma unroll
@@ -208,17 +231,17 @@ __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], cons
 	for (int off = 32; off > 0; off >>= 1) occ = max(occ, (uint32_t)__shfl_xor((int)occ, off));
 	if (lane == 63) s_wave[wid] = sc;
 	if (lane == 0) s_occ[wid] = occ;
-	__syncthreads();
+	group_sync<GROUPS>();
 	uint32_t run = sc - sum;
 #pragma unroll
 	for (int w = 0; w < NW; w++) { if (w < wid) run += s_wave[w]; occ = max(occ, s_occ[w]); }
 #pragma unroll
 	for (int k = 0; k < PER; k++) { const uint32_t c = hist[tid * PER + k]; hist[tid * PER + k] = run; run += c; }
-	__syncthreads();
+	group_sync<GROUPS>();
 #pragma unroll
 	for (int t = 0; t < ITEMS; t++)
 		if (tid + t * THREADS < n) rk[t] += hist[bucket_of(key[t])];
-	__syncthreads(); // the histogram has been read: the keys take its place
+	group_sync<GROUPS>(); // the histogram has been read: the keys take its place
 #pragma unroll
 	for (int t = 0; t < ITEMS; t++)
 		if (tid + t * THREADS < n) sk[sk_slot<ITEMS>((int)rk[t])] = key[t];
@@ -226,11 +249,11 @@ __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], cons
 	{
 		const int nact = msort_active<THREADS, ITEMS>(n);
 		for (int i = n + tid; i < nact; i += THREADS) sk[sk_slot<ITEMS>(i)] = ~0ull;
-		__syncthreads();
-		msort_lds<THREADS, ITEMS>(sk, nact);
+		group_sync<GROUPS>();
+		msort_lds<THREADS, ITEMS, GROUPS>(sk, nact);
 		return;
 	}
-	__syncthreads();
+	group_sync<GROUPS>();
 	if (occ < 2u) return;
 	for (uint32_t r = 0; r < occ; r++)
 	{
@@ -240,23 +263,24 @@ __device__ __forceinline__ void sort_keys_lds(const uint64_t (&key)[ITEMS], cons
 			const uint64_t x = sk[ia], y = sk[ib];
 			if (x > y) { sk[ia] = y; sk[ib] = x; }
 		}
-		__syncthreads();
+		group_sync<GROUPS>();
 	}
 }
 
 // One list of n keys (entries + rg.x ..) sorted into point_list by the whole workgroup; LDS (sk) holds THREADS x ITEMS keys
 // (+ the spare slots). fallback: a list that does not fit is sorted in place in global memory by the bitonic network (chunks
 // of a split list with thousands of equal depths); otherwise such a list is left to another kernel.
-template <int THREADS, int ITEMS, bool FALLBACK>
+template <int THREADS, int ITEMS, bool FALLBACK, int GROUPS = 1>
 __device__ __forceinline__ void msort_list(const uint2 rg, uint64_t *entries, uint32_t *point_list, uint64_t *sk)
 {
 	const int n = (int)(rg.y - rg.x);
-	const int tid = threadIdx.x;
+	const int tid = group_tid<THREADS, GROUPS>();
 	uint64_t *src = entries + rg.x;
 	uint32_t *dst = point_list + rg.x;
 	if (n > THREADS * ITEMS)
 	{
 		if (!FALLBACK) return;
+		static_assert(!FALLBACK || GROUPS == 1, "the network in global memory takes the whole workgroup");
 		int npow2 = 1;
 		while (npow2 < n) npow2 <<= 1;
 		bitonic_sort<true>(src, n, npow2, tid, THREADS);
@@ -266,7 +290,7 @@ __device__ __forceinline__ void msort_list(const uint2 rg, uint64_t *entries, ui
 	uint64_t key[ITEMS];
 #pragma unroll
 	for (int t = 0; t < ITEMS; t++) { const int i = tid + t * THREADS; key[t] = i < n ? src[i] : ~0ull; }
-	sort_keys_lds<THREADS, ITEMS>(key, n, sk);
+	sort_keys_lds<THREADS, ITEMS, GROUPS>(key, n, sk);
 	for (int i = tid; i < n; i += THREADS) dst[i] = (uint32_t)sk[sk_slot<ITEMS>(i)];
 }
 
