@@ -1,6 +1,7 @@
 // extern "C" entry points of libfovraster_hip.so (see include/fovraster.h for the contract and
 // for the reference interfaces each one replaces).
 #include "common.h"
+#include <atomic>
 #include <mutex>
 #include <cstdarg>
 #include <cstdio>
@@ -160,7 +161,8 @@ static PinnedBlock *take_pinned(int device)
 			if (hipEventQuery(b.quarantine) != hipSuccess) { (void)hipGetLastError(); continue; }
 			b.quarantined = false;
 		}
-		if (b.host && b.device == device) { b.busy = true; return &b; }
+		// (an idle block still holds its last frame's sequence word; no write to it is in flight: not busy, not quarantined)
+		if (b.host && b.device == device) { __atomic_store_n(&b.host[4], 0u, __ATOMIC_RELEASE); b.busy = true; return &b; }
 		if (!spare) spare = &b;
 	}
 	if (!spare) return nullptr; // every block of the pool in flight: the frame falls back to a copy + stream wait
@@ -291,9 +293,12 @@ int fr_forward_begin(fr_forward_args *a, fr_frame **out)
 		FR_HIP(hipMemsetAsync(c.geom.slab_ctr, 0, FR_SLAB_CTR_WORDS * sizeof(uint32_t), stream));
 	if (a->list_consumed) FR_HIP(hipMemsetAsync(a->list_consumed, 0, sizeof(uint32_t) * (size_t)c.T, stream));
 	if (a->blend_pairs) FR_HIP(hipMemsetAsync(a->blend_pairs, 0, sizeof(uint32_t) * (size_t)c.T, stream));
-	static thread_local uint32_t frame_seq = 0; // this frame's tag: the totals block's sequence word
-	if (++frame_seq == 0) frame_seq = 1;
-	c.totals_seq = frame_seq;
+	// this frame's tag, the totals block's sequence word: one counter per PROCESS, as the pool of blocks is -- no two frames in flight,
+	// whatever threads they belong to, share a tag, and a block never holds the tag of the frame that takes it (0 is never a tag)
+	static std::atomic<uint32_t> frame_seq{0};
+	uint32_t seq = frame_seq.fetch_add(1, std::memory_order_relaxed) + 1;
+	while (seq == 0) seq = frame_seq.fetch_add(1, std::memory_order_relaxed) + 1;
+	c.totals_seq = seq;
 	mark(FR_STAGE_TILE_LEVELS);
 	if (is_fov(a->variant)) { rc = launch_tile_levels(c); if (rc) return rc; }
 	mark(FR_STAGE_PROJECT);

@@ -1047,6 +1047,9 @@ int launch_backward(const fr_backward_args *a)
 	{
 		hipLaunchKernelGGL(k_preprocess_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
 		rc2 = check_launch("preprocess_bwd", stream, a->debug);
+		// a host that asked to be told is told, whatever made the pass run in one piece (num_ranges <= 1, P < 64 num_ranges): every
+		// row is complete behind this launch (the rows of a row-sparse call are not Gaussian indices: no call)
+		if (!rc2 && a->range_done != nullptr && !a->row_sparse) a->range_done(a->range_user, 0, 0, a->P);
 	}
 	mark(2);
 	return rc2;

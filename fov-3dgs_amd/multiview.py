@@ -122,7 +122,7 @@ def allreduce_gradients_flat(params, timings=None):
     return dict(mode="flat", bytes=n * flat.element_size())
 
 
-def _allreduce_sparse_rows(params):
+def _allreduce_sparse_rows(params, group=None):
     """Gradients that already ARE row-sparse (the rasterizer's row_sparse extension: torch.sparse_coo with one sparse dimension,
     the Gaussians this rank's view touched): exchanged as the rows of the union of the ranks' row sets -- no dense [P, ...]
     tensor is ever made. p.grad becomes the summed sparse tensor over the union's rows (the same rows on every rank)."""
@@ -131,7 +131,7 @@ def _allreduce_sparse_rows(params):
     union = torch.zeros(P, dtype=torch.uint8, device=dev)
     for g in grads:
         union[g.indices()[0]] = 1
-    dist.all_reduce(union, op=dist.ReduceOp.MAX)
+    dist.all_reduce(union, op=dist.ReduceOp.MAX, group=group)
     idx = torch.nonzero(union, as_tuple=False).squeeze(1)
     U = int(idx.numel())
     widths = [g.values()[0].numel() if g.values().shape[0] else int(torch.tensor(g.shape[1:]).prod().item()) for g in grads]
@@ -141,7 +141,7 @@ def _allreduce_sparse_rows(params):
         pos = torch.searchsorted(idx, g.indices()[0])
         rows[pos, off:off + w] = g.values().reshape(-1, w)
         off += w
-    dist.all_reduce(rows, op=dist.ReduceOp.SUM)
+    dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=group)
     off = 0
     for p_, g, w in zip(params, grads, widths):
         p_.grad = torch.sparse_coo_tensor(idx.unsqueeze(0), rows[:, off:off + w].reshape((U,) + tuple(g.shape[1:])), g.shape, is_coalesced=True)
@@ -149,7 +149,7 @@ def _allreduce_sparse_rows(params):
     return dict(mode="sparse_rows", rows=U, of=P, bytes=rows.numel() * rows.element_size() + P)
 
 
-def allreduce_gradients(params, visible=None, sparse_below=0.4, check_rows=False, per_tensor_ms=None):
+def allreduce_gradients(params, visible=None, sparse_below=0.4, check_rows=False, per_tensor_ms=None, group=None):
     """Sum the per-view gradients of the replicated parameters over all ranks. -> dict with what was exchanged.
 
     dense (default): every gradient tensor is all-reduced IN PLACE, all collectives in flight at once (no flat copy: the
@@ -165,18 +165,19 @@ def allreduce_gradients(params, visible=None, sparse_below=0.4, check_rows=False
     accumulation or a dense loss term (opacity / scale regularisers, a mask loss) rows outside the union would be left
     un-summed -- use the dense exchange (visible=None) there. check_rows=True verifies the precondition (one reduction
     per tensor and a host sync: for tests and debugging). per_tensor_ms: optional list that receives (numel, milliseconds) of
-    every tensor's all-reduce, issued one after the other and timed with CUDA events (diagnosis: which tensor dominates)."""
-    if not dist.is_initialized() or dist.get_world_size() == 1:
+    every tensor's all-reduce, issued one after the other and timed with CUDA events (diagnosis: which tensor dominates).
+    group: the process group to sum over (None: the default group)."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
         return dict(mode="none", bytes=0)
     grads = [p.grad for p in params if p.grad is not None]
     if not grads:
         return dict(mode="none", bytes=0)
     P = grads[0].shape[0]
     if all(g.is_sparse for g in grads):
-        return _allreduce_sparse_rows([p for p in params if p.grad is not None])
+        return _allreduce_sparse_rows([p for p in params if p.grad is not None], group)
     if visible is not None and all(g.shape[0] == P for g in grads):
         union = visible.to(torch.uint8)
-        dist.all_reduce(union, op=dist.ReduceOp.MAX)
+        dist.all_reduce(union, op=dist.ReduceOp.MAX, group=group)
         idx = torch.nonzero(union, as_tuple=False).squeeze(1)
         U = int(idx.numel())
         if U < sparse_below * P:
@@ -192,7 +193,7 @@ def allreduce_gradients(params, visible=None, sparse_below=0.4, check_rows=False
             for g, w in zip(grads, widths):
                 rows[:, off:off + w] = g.reshape(P, w).index_select(0, idx)
                 off += w
-            dist.all_reduce(rows, op=dist.ReduceOp.SUM)
+            dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=group)
             off = 0
             for g, w in zip(grads, widths):
                 g.reshape(P, w).index_copy_(0, idx, rows[:, off:off + w])
@@ -203,13 +204,13 @@ def allreduce_gradients(params, visible=None, sparse_below=0.4, check_rows=False
         for g in grads:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            dist.all_reduce(g, op=dist.ReduceOp.SUM)
+            dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
             e1.record()
             evs.append((g.numel(), e0, e1))
         torch.cuda.synchronize()
         per_tensor_ms.extend((n_, e0.elapsed_time(e1)) for n_, e0, e1 in evs)
         return dict(mode="dense", bytes=sum(g.numel() * g.element_size() for g in grads))
-    works = [dist.all_reduce(g, op=dist.ReduceOp.SUM, async_op=True) for g in grads]
+    works = [dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group, async_op=True) for g in grads]
     for w in works:
         w.wait()
     return dict(mode="dense", bytes=sum(g.numel() * g.element_size() for g in grads))
@@ -237,7 +238,11 @@ class OverlappedGradientExchange:
     keys name the rasterizer's inputs; a parameter may be missing (None). PRECONDITION: p.grad is None on entry (no accumulation: the
     sum is formed in the tensors the backward call allocates). If autograd copied a tensor instead of adopting it, p.grad is set
     to the summed tensor on exit. One backward call of one rasterizer per `with` block. Works on CPU tensors / gloo as well
-    (synchronous collectives: the tests)."""
+    (synchronous collectives: the tests).
+    The sum ALWAYS happens: the library reports a pass that runs in one piece (ranges <= 1, fewer than 64 * ranges Gaussians) as one
+    range over every row, and a block in which no range was reported at all (row-sparse gradients, an empty model, gradients that did
+    not come from the rasterizer) ends with allreduce_gradients over the parameters that have a gradient -- not overlapped, but never
+    skipped. ex.fallback tells which of the two a block took."""
 
     def __init__(self, params, ranges=4, group=None):
         self.params = {k: v for k, v in params.items() if v is not None}
@@ -245,6 +250,7 @@ class OverlappedGradientExchange:
         self.comm = None
         self._tensors, self._works, self._events = None, [], None
         self.calls = []
+        self.fallback = None  # allreduce_gradients' result when the last block ended with it (no range was reported), else None
 
     def _active(self):
         return dist.is_initialized() and dist.get_world_size(self.group) > 1
@@ -254,7 +260,7 @@ class OverlappedGradientExchange:
         for k, p_ in self.params.items():
             if p_.grad is not None:
                 raise RuntimeError(f"OverlappedGradientExchange: {k}.grad must be None on entry (the sum is formed in the backward call's own tensors)")
-        self._tensors, self._works, self.calls = None, [], []
+        self._tensors, self._works, self.calls, self.fallback, self._events = None, [], [], None, None
         if self._active():
             self._saved = (rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES)
             rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES = self._on_range, self.ranges
@@ -289,9 +295,15 @@ class OverlappedGradientExchange:
         from . import rasterizer as rz
         if self._active():
             rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES = self._saved
-        if exc_type is not None or self._tensors is None:
+        if exc_type is not None:
             for w in self._works:
                 w.wait()
+            return False
+        if self._tensors is None:
+            # no range was reported (row-sparse gradients: the rasterizer installs no hook; P == 0: the library is not called): the
+            # ranks must not go on with their own view's gradients alone, so the sum is made here, behind the backward pass
+            if self._active():
+                self.fallback = allreduce_gradients(list(self.params.values()), group=self.group)
             return False
         cuda = any(t is not None and t.is_cuda for t in self._tensors.values())
         if cuda:

@@ -359,7 +359,8 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
     set of this (device, stream, thread) (valid until the next call there); otherwise they stay reserved for as long as the
     `lease` of the result is referenced.
     reuse / reuse_key (the overlapped inference path): `reuse` is a dict the caller keeps per internal stream; when its "key" equals
-    reuse_key -- the caller vouches that every tensor, scalar and flag of the call is what it was at the previous call on that stream --
+    reuse_key -- the caller vouches that every tensor, scalar and flag of the call is what it was at the previous call on that stream, and
+    clears the dict whenever a tensor OBJECT changed (the key alone cannot tell a new tensor at a dead one's id and address) --
     the argument struct made then is used again with only the gaze and the two output tensors replaced (filling it is 20 checked
     tensor arguments: 40 us of host time on a path where the host is the bottleneck)."""
     lib = _native.load()
@@ -571,6 +572,12 @@ def _forward_overlapped(args, kw):
         ev = torch.cuda.Event()
         ev.record(cur)
         st.must_wait = [ev] * len(st.streams)
+        # ... and none of them uses its previous frame's argument struct again: a struct points at the converted copies of that frame's
+        # camera tensors, and its key is made of ids, addresses and version counters, which a NEW tensor can repeat once the old one is
+        # gone (a host that builds a camera per frame). A struct that survives was therefore made after the last change of inputs, and
+        # every call since has proved through st.refs that the very objects it was made from are alive.
+        for r in st.reuse:
+            r.clear()
         st.sig = None if outputs else sig
         import weakref
         st.refs = [weakref.ref(t) for t in tensors]

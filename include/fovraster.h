@@ -245,8 +245,11 @@ typedef struct fr_backward_args {
 	 * the HOST function range_done(range_user, k, row_lo, row_hi) is called (from inside fr_backward, on the calling thread): a host
 	 * records an event there and starts summing those rows over its ranks on a communication stream while the later ranges are still
 	 * being computed. Range k starts at row (P k / num_ranges) rounded down to a multiple of 32 (the visible list is in index order,
-	 * so a range of rows is a range of list entries): equal shares of the INDEX range, not of the visible Gaussians. Dense
-	 * gradients only (ignored with row_sparse); at most 16 ranges. 0 / 1 or range_done == NULL: one piece, no call. */
+	 * so a range of rows is a range of list entries): equal shares of the INDEX range, not of the visible Gaussians. At most 16
+	 * ranges. The pass runs in ONE piece when num_ranges is 0 or 1 and when P < 64 * num_ranges; range_done, when given, is then
+	 * still called, exactly once, as range_done(range_user, 0, 0, P) behind the single launch: a host that sums what it is told
+	 * about never misses rows. Dense gradients only: with row_sparse (the rows are not Gaussian indices), with
+	 * range_done == NULL and with P == 0 (fr_backward returns at once: there is no row to report) there is no call. */
 	int32_t num_ranges;
 	void (*range_done)(void *user, int32_t k, int32_t row_lo, int32_t row_hi);
 	void *range_user;

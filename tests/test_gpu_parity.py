@@ -509,13 +509,16 @@ def test_narrow_gradient_tensors_with_clustered_visibility(P):
         assert np.abs(dense[k]).max() > 0, k
 
 
-@pytest.mark.parametrize("P", (20000, 777))
-def test_backward_in_ranges_of_rows(P):
+@pytest.mark.parametrize("P,ranges", [pytest.param(20000, 4, id="20000"), pytest.param(777, 4, id="777"), pytest.param(200, 4, id="200"),
+                                      pytest.param(777, 1, id="777-one-range")])
+def test_backward_in_ranges_of_rows(P, ranges):
     """fr_backward_args.num_ranges / range_done (round 6; rasterizer.GRADIENT_RANGE_HOOK): the per-Gaussian half of the backward call in
     four pieces over increasing ranges of rows, the host told behind each piece. The ranges tile [0, P) in order, start on multiples of
     32 (a group of the whole-line scheme never straddles two) and the gradients -- clustered visibility, every tensor NaN before the
     call -- are those of the call in one piece. A tensor snapshot taken INSIDE the callback (a copy enqueued on the stream right
-    there) already holds the final rows of its range: that is what lets a communication stream start on them."""
+    there) already holds the final rows of its range: that is what lets a communication stream start on them.
+    A pass that runs in ONE piece although the host asked to be told -- fewer than 64 Gaussians per range (P = 200, four ranges), or one
+    range asked for -- still tells it, exactly once, about every row: (0, 0, P). A host that sums what it is told about misses nothing."""
     _need_gpu()
     from fov3dgs_amd import rasterizer as rz
     from fov3dgs_amd.gaussian_renderer import render
@@ -547,24 +550,29 @@ def test_backward_in_ranges_of_rows(P):
         def hook(k, lo, hi, grads):
             calls.append((k, lo, hi))
             snaps.append({n: t[lo:hi].clone() for n, t in grads.items() if t is not None})
-        rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES = (hook if ranged else None), 4
+        rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES = (hook if ranged else None), ranges
         try:
             (out["render"] * w).sum().backward()
         finally:
-            rz.GRADIENT_RANGE_HOOK = None
+            rz.GRADIENT_RANGE_HOOK, rz.GRADIENT_RANGES = None, 4
         torch.cuda.synchronize()
         grads = dict(means3D=cloud._xyz.grad, scales=cloud._scaling.grad, rotations=cloud._rotation.grad, opacities=cloud._opacity.grad,
                      sh=cloud._features_dc.grad, sh_rest=cloud._features_rest.grad)
         res.append(({k: g.clone() for k, g in grads.items()}, calls, snaps))
     (one, c0, _), (four, calls, snaps) = res
-    assert c0 == [] and [c[0] for c in calls] == [0, 1, 2, 3]
+    one_piece = ranges <= 1 or P < 64 * ranges
+    assert c0 == [] and [c[0] for c in calls] == ([0] if one_piece else [0, 1, 2, 3])
+    if one_piece:
+        assert calls == [(0, 0, P)]
     assert calls[0][1] == 0 and calls[-1][2] == P and all(a[2] == b[1] for a, b in zip(calls, calls[1:]))
     assert all(lo % 32 == 0 for _, lo, _ in calls) and all(hi > lo for _, lo, hi in calls)
     for k in one:
         assert torch.isfinite(four[k]).all(), k
         check_grad(four[k].cpu().numpy(), one[k].cpu().numpy(), "backward in four ranges vs one piece: " + k)
+        assert len(snaps) == len(calls)
         for (kk, lo, hi), snap in zip(calls, snaps):
             assert torch.equal(snap[k], four[k][lo:hi]), (k, kk)   # the rows of a range were final when the host was told
+        assert float(one[k].abs().max()) > 0, k
 
 
 @pytest.mark.parametrize("variant", ["original", "pcheck_obb_sum"])

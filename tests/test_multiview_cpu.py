@@ -104,6 +104,39 @@ def _worker(rank, world, port, q):
         for p_, k_ in zip(ref, [k for k, v in named.items() if v is not None]):
             assert torch.equal(named[k_].grad, p_.grad), (adopt, k_)
         assert torch.equal(grads["rotations"], mine["rotations"])
+    # a block in which NOBODY calls the hook (the backward pass ran in one piece without reporting it, or returned row-sparse
+    # gradients, for which the rasterizer installs no hook): the gradients autograd leaves in p.grad are this rank's alone, and the
+    # block must still end with their sum over the ranks -- the same as allreduce_gradients makes of clones
+    for sparse in (False, True):
+        named = {"means3D": torch.nn.Parameter(torch.zeros(Pn, 3)), "opacities": torch.nn.Parameter(torch.zeros(Pn, 1)),
+                 "sh_rest": torch.nn.Parameter(torch.zeros(Pn, 15, 3)), "scales": None}
+        live = [k for k, v in named.items() if v is not None]
+        if sparse:
+            rows = torch.tensor([rank, 7, 500 + rank, Pn - 1 - 3 * rank])  # increasing and unique; rows 7 shared, the others one rank's
+            mine = {k: torch.sparse_coo_tensor(rows.unsqueeze(0), torch.randn((4,) + tuple(named[k].shape[1:]), generator=gen), named[k].shape)
+                    for k in live}
+        else:
+            mine = {k: torch.randn(named[k].shape, generator=gen) for k in live}
+        ref = [torch.nn.Parameter(torch.zeros_like(named[k])) for k in live]
+        for p_, k_ in zip(ref, live):
+            p_.grad = mine[k_].clone()
+        info_r = multiview.allreduce_gradients(ref)
+        assert info_r["mode"] == ("sparse_rows" if sparse else "dense")
+        ex = multiview.OverlappedGradientExchange(named, ranges=4)
+        with ex:
+            assert rz.GRADIENT_RANGE_HOOK is not None
+            for k_ in live:
+                named[k_].grad = mine[k_].clone()
+        assert rz.GRADIENT_RANGE_HOOK is None and ex.calls == []
+        for p_, k_ in zip(ref, live):
+            got, want = named[k_].grad, p_.grad
+            assert got.is_sparse == sparse, (sparse, k_)
+            if sparse:
+                got, want = got.to_dense(), want.to_dense()
+            assert torch.equal(got, want), ("no range reported", sparse, k_)
+            own = mine[k_].to_dense() if sparse else mine[k_]
+            assert not torch.equal(got, own), ("the other rank's share is missing", sparse, k_)
+        assert ex.fallback is not None and ex.fallback["mode"] == info_r["mode"] and ex.fallback["bytes"] == info_r["bytes"]
     try:
         busy = {"means3D": torch.nn.Parameter(torch.zeros(4, 3))}
         busy["means3D"].grad = torch.zeros(4, 3)

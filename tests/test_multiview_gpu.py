@@ -129,6 +129,97 @@ def test_two_views_training_step_and_gradient_sum():
     assert all(p.exitcode == 0 for p in procs)
 
 
+def _one_piece_worker(rank, world, port, q):
+    """The exchange inside the backward pass where the pass runs in ONE piece: (i) fewer than 64 Gaussians per range, (ii) one range
+    asked for, (iii) row-sparse gradients (no hook at all). Each rank renders its view of the ring with a model whose rasterizer inputs
+    are its leaf parameters, sums inside `with ex:`, then repeats both views alone."""
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                          LOCAL_RANK=str(rank), LOCAL_WORLD_SIZE=str(world))
+        import torch.distributed as dist
+        import fov3dgs_amd  # noqa: F401
+        from fov3dgs_amd import multiview, synthetic as syn
+        from fov3dgs_amd.gaussian_renderer import render
+        from fov3dgs_amd.loss_utils import l1_ssim_loss
+        r, w, local = multiview.init_distributed()
+        assert (r, w) == (rank, world)
+        dev = torch.device("cuda", local)
+        torch.cuda.set_device(dev)
+        W, H = 320, 192
+        worst = {}
+        for name, P, ranges, sparse in (("P=200 ranges=4", 200, 4, False), ("P=5000 ranges=1", 5000, 1, False), ("P=5000 row-sparse", 5000, 4, True)):
+            cloud_cpu = syn.scene_bicycle_scale(P=P, seed=1, scale_log_mean=-3.2)
+
+            def fused_view(view, exchange):
+                cloud = cloud_cpu.to(dev).requires_grad_(True)
+                cloud.fuse_activations = True
+                cloud.row_sparse_grads = sparse
+                cam = syn.camera_ring(view, 8, W, H).to(dev)
+                target = torch.rand(3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(100 + view))
+                out = render(cam, cloud, _Pipe(), torch.zeros(3, device=dev), cuda_type="pcheck_obb_sum")
+                loss = l1_ssim_loss(out["render"], target, 0.2)
+                if exchange:
+                    ex = multiview.OverlappedGradientExchange({"means3D": cloud._xyz, "opacities": cloud._opacity, "scales": cloud._scaling,
+                                                               "rotations": cloud._rotation, "sh": cloud._features_dc, "sh_rest": cloud._features_rest},
+                                                              ranges=ranges)
+                    with ex:
+                        loss.backward()
+                    if sparse:   # nobody was told anything: the block ended with allreduce_gradients over the sparse rows
+                        assert ex.calls == [] and ex.fallback is not None and ex.fallback["mode"] == "sparse_rows", (ex.calls, ex.fallback)
+                    else:        # the library reported its single piece as one range over every row
+                        assert ex.calls == [(0, 0, P)] and ex.fallback is None, (ex.calls, ex.fallback)
+                else:
+                    loss.backward()
+                torch.cuda.synchronize()
+                grads = [p.grad for p in cloud.parameters()]
+                assert all(g is not None and g.is_sparse == sparse for g in grads), name
+                return [g.to_dense() if sparse else g for g in grads]
+            summed = fused_view(rank, True)
+            a_, b_ = fused_view(rank, False), fused_view(1 - rank, False)
+            for i, (gs, ga, gb) in enumerate(zip(summed, a_, b_)):
+                want = ga + gb
+                assert float(want.abs().max()) > 0, (name, i)
+                err = float((gs - want).abs().max()) / (float(want.abs().max()) + 1e-12)
+                worst[name] = max(worst.get(name, 0.0), err)
+                # float atomics make a view's gradient sums order-dependent in the last bits; nothing else differs
+                assert err < 2e-5, (name, i, err)
+        q.put((rank, worst, None))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception as e:  # noqa: BLE001 -- the parent must see why a rank died
+        import traceback
+        q.put((rank, {}, traceback.format_exc()))
+        raise e
+
+
+@pytest.mark.timeout(300)
+def test_gradient_sum_when_the_backward_pass_runs_in_one_piece():
+    """multiview.OverlappedGradientExchange on two ranks where fr_backward never splits its per-Gaussian pass: too few Gaussians for the
+    ranges asked for, one range, row-sparse gradients. The exchange used to return without any all-reduce in all three (no range was
+    ever reported) and the ranks went on with their own view's gradients; the summed gradients must be the own view's plus the other
+    view's, both computed alone on the same rank, within 2e-5 of the tensor's largest magnitude (float atomics reorder the sums)."""
+    world, port = 2, _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_one_piece_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = sorted((q.get(timeout=240) for _ in range(world)), key=lambda t: t[0])
+        for p in procs:
+            p.join(60)
+    finally:
+        for p in procs:  # (a rank that died inside a collective leaves the other one waiting for it)
+            if p.is_alive():
+                p.kill()
+                p.join(10)
+    for rank, worst, err in res:
+        assert err is None, err
+        assert len(worst) == 3 and all(0.0 <= v < 2e-5 for v in worst.values()), worst
+    assert all(p.exitcode == 0 for p in procs)
+
+
 @pytest.mark.timeout(900)
 def test_bench_train_mode_two_ranks_share_the_gpu():
     """`bench.py --gpus 2 --mode train` as the driver starts it (no torchrun environment): the launcher, two ranks, one
