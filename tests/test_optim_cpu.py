@@ -38,7 +38,7 @@ def test_adam_structs_match_c_layout(tmp_path):
     for f, off in zip(fa, nums[k + 1:k + 1 + len(fa)]):
         assert getattr(_native.AdamArgs, f).offset == off, f
     assert nums[-5:] == [_native.ADAM_MAX_TENSORS, _native.ADAM_DENSE, _native.ADAM_EXACT, _native.ADAM_LAZY, _native.ABI_VERSION]
-    assert _native.ABI_VERSION == 11
+    assert _native.ABI_VERSION == 12
 
 
 def test_native_rejects_bad_tables_without_launching():

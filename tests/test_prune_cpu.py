@@ -25,7 +25,7 @@ def test_header_library_and_exports_carry_the_new_symbols():
     lib = _native.load()
     for n in NEW:
         assert n in declared and n in _native.EXPORTS and hasattr(lib, n), n
-    assert lib.fr_abi_version() == 11  # symbols were added, no existing struct changed
+    assert lib.fr_abi_version() == 12
 
 
 def test_compact_structs_and_constants_match_c_layout(tmp_path):
