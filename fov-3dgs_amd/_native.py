@@ -110,13 +110,37 @@ class CompactArgs(C.Structure):
                 ("mask", _FP), ("workspace", _FP), ("tensors", CompactTensor * COMPACT_MAX_TENSORS)]
 
 
+DENSIFY_CLONE_MASK, DENSIFY_SPLIT_MASK, DENSIFY_CLONE_GRAD, DENSIFY_SPLIT_GRAD, DENSIFY_AND_PRUNE = 0, 1, 2, 3, 4
+DENSIFY_COPY, DENSIFY_ZERO_NEW, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2, 3
+
+
+class DensifyPlanArgs(C.Structure):
+    _fields_ = [("P", C.c_int32), ("mode", C.c_int32), ("N", C.c_int32), ("use_world_size", C.c_int32),
+                ("n_grad", C.c_int32), ("reserved", C.c_int32),
+                ("max_grad", C.c_float), ("min_opacity", C.c_float), ("t_dense", C.c_float), ("t_world", C.c_float),
+                ("accum", _FP), ("denom", _FP), ("scaling", _FP), ("opacity", _FP), ("mask", _FP),
+                ("counts_out", _FP), ("workspace", _FP)]
+
+
+class DensifyTensor(C.Structure):
+    _fields_ = [("src", _FP), ("dst", _FP), ("row_words", C.c_int32), ("role", C.c_int32)]
+
+
+class DensifyRowsArgs(C.Structure):
+    _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("num_tensors", C.c_int32), ("reserved", C.c_int32),
+                ("n_keep", C.c_int32), ("n_clone", C.c_int32), ("n_split", C.c_int32), ("n_child", C.c_int32),
+                ("scaling", _FP), ("rotation", _FP), ("noise", _FP), ("workspace", _FP),
+                ("tensors", DensifyTensor * COMPACT_MAX_TENSORS)]
+
+
 EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destroy", "fr_event_elapsed_ms", "fr_forward", "fr_backward", "fr_mark_visible", "fr_pack_geom", "fr_pack_colour", "fr_pack_cull", "fr_activate_forward", "fr_activate_backward", "fr_l1_ssim_blocks", "fr_l1_ssim_forward", "fr_l1_ssim_finish", "fr_l1_ssim_backward",
            "fr_geometry_bytes", "fr_image_bytes", "fr_binning_bytes", "fr_image_ranges",
            "fr_binning_point_list", "fr_image_final_T", "fr_image_n_contrib", "fr_image_tile_levels", "fr_geometry_records",
            "fr_geometry_vis_list", "fr_geometry_vis_count", "fr_geometry_walk_records", "fr_geometry_level_colours",
            "fr_geometry_level_ranges", "fr_forward_begin", "fr_forward_finish", "fr_forward_abandon", "fr_backward_prefill",
            "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step",
-           "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows")
+           "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows",
+           "fr_densify_workspace_bytes", "fr_densify_stats", "fr_densify_plan", "fr_densify_rows")
 
 _lib = None
 
@@ -218,6 +242,14 @@ def load():
     lib.fr_compact_plan.restype = C.c_int
     lib.fr_compact_rows.argtypes = [C.POINTER(CompactArgs), C.c_void_p]
     lib.fr_compact_rows.restype = C.c_int
+    lib.fr_densify_workspace_bytes.argtypes = [C.c_int32]
+    lib.fr_densify_workspace_bytes.restype = C.c_size_t
+    lib.fr_densify_stats.argtypes = [C.c_int32, _FP, _FP, _FP, _FP, C.c_void_p]
+    lib.fr_densify_stats.restype = C.c_int
+    lib.fr_densify_plan.argtypes = [C.POINTER(DensifyPlanArgs), C.c_void_p]
+    lib.fr_densify_plan.restype = C.c_int
+    lib.fr_densify_rows.argtypes = [C.POINTER(DensifyRowsArgs), C.c_void_p]
+    lib.fr_densify_rows.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -568,6 +568,65 @@ int fr_compact_rows(const fr_compact_args *a, void *stream)
 	return launch_compact_rows(a, (hipStream_t)stream);
 }
 
+size_t fr_densify_workspace_bytes(int32_t P) { return densify_workspace_bytes(P); }
+
+int fr_densify_stats(int32_t P, const float *grad, const uint8_t *update_filter, float *accum, float *denom, void *stream)
+{
+	if (P < 0) { set_error("densify_stats: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (P > 0 && (!grad || !update_filter || !accum || !denom)) { set_error("densify_stats: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_densify_stats(P, grad, update_filter, accum, denom, (hipStream_t)stream);
+}
+
+int fr_densify_plan(const fr_densify_plan_args *a, void *stream)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (a->P < 0) { set_error("densify_plan: bad size P=%d", a->P); return FR_ERR_INVALID; }
+	if (a->mode < FR_DENSIFY_CLONE_MASK || a->mode > FR_DENSIFY_AND_PRUNE) { set_error("densify_plan: unknown mode %d", a->mode); return FR_ERR_INVALID; }
+	if (a->N < 1 || a->N > 4) { set_error("densify_plan: N=%d is not in 1..4", a->N); return FR_ERR_INVALID; }
+	if (a->P == 0) return FR_OK; // (nothing launched: counts_out is not written)
+	if (!a->counts_out || !a->workspace) { set_error("densify_plan: counts_out or workspace is null"); return FR_ERR_INVALID; }
+	if ((uintptr_t)a->workspace % 16) { set_error("densify workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	const bool by_mask = a->mode == FR_DENSIFY_CLONE_MASK || a->mode == FR_DENSIFY_SPLIT_MASK;
+	if (by_mask && !a->mask) { set_error("densify_plan: mode %d needs a mask", a->mode); return FR_ERR_INVALID; }
+	if (!by_mask)
+	{
+		if (a->n_grad < 0 || a->n_grad > a->P) { set_error("densify_plan: n_grad=%d is not in 0..P=%d", a->n_grad, a->P); return FR_ERR_INVALID; }
+		if (!a->scaling || (a->n_grad > 0 && !a->accum)) { set_error("densify_plan: scaling or accum is null"); return FR_ERR_INVALID; }
+		if (a->mode == FR_DENSIFY_AND_PRUNE && (!a->opacity || !a->denom || a->n_grad != a->P))
+		{ set_error("densify_plan: densify_and_prune needs opacity, denom and n_grad = P"); return FR_ERR_INVALID; }
+	}
+	return launch_densify_plan(a, (hipStream_t)stream);
+}
+
+int fr_densify_rows(const fr_densify_rows_args *a, void *stream)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (a->P < 0) { set_error("densify_rows: bad size P=%d", a->P); return FR_ERR_INVALID; }
+	if (a->N < 1 || a->N > 4) { set_error("densify_rows: N=%d is not in 1..4", a->N); return FR_ERR_INVALID; }
+	if (a->num_tensors < 0 || a->num_tensors > FR_COMPACT_MAX_TENSORS) { set_error("densify_rows: %d tensors (at most %d)", a->num_tensors, FR_COMPACT_MAX_TENSORS); return FR_ERR_INVALID; }
+	if (a->n_keep < 0 || a->n_keep > a->P || a->n_clone < 0 || a->n_clone > a->P || a->n_split < 0 || a->n_split > a->P || a->n_child < 0 || a->n_child > a->n_split)
+	{ set_error("densify_rows: bad counts (keep=%d clone=%d split=%d child=%d P=%d)", a->n_keep, a->n_clone, a->n_split, a->n_child, a->P); return FR_ERR_INVALID; }
+	const int64_t rows = (int64_t)a->n_keep + a->n_clone + (int64_t)a->N * a->n_child;
+	if (rows > 0x7fffffff) { set_error("densify_rows: %lld output rows do not fit an int32", (long long)rows); return FR_ERR_INVALID; }
+	if (a->P == 0 || a->num_tensors == 0 || rows == 0) return FR_OK;
+	if (!a->workspace) { set_error("densify_rows: workspace is null"); return FR_ERR_INVALID; }
+	if ((uintptr_t)a->workspace % 16) { set_error("densify workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	for (int k = 0; k < a->num_tensors; k++)
+	{
+		const fr_densify_tensor &t = a->tensors[k];
+		if (t.row_words < 0 || t.role < FR_DENSIFY_COPY || t.role > FR_DENSIFY_SCALING) { set_error("densify_rows: tensor %d: bad row_words=%d or role=%d", k, t.row_words, t.role); return FR_ERR_INVALID; }
+		if (t.row_words > 0 && (!t.src || !t.dst)) { set_error("densify_rows: tensor %d: a data pointer is null", k); return FR_ERR_INVALID; }
+		if (t.role >= FR_DENSIFY_XYZ)
+		{
+			if (t.row_words != 3) { set_error("densify_rows: tensor %d: role %d needs rows of 3 words, not %d", k, t.role, t.row_words); return FR_ERR_INVALID; }
+			if (a->n_child > 0 && (!a->scaling || (t.role == FR_DENSIFY_XYZ && (!a->rotation || !a->noise))))
+			{ set_error("densify_rows: tensor %d: role %d needs scaling (xyz: rotation and noise too)", k, t.role); return FR_ERR_INVALID; }
+		}
+	}
+	return launch_densify_rows(a, (hipStream_t)stream);
+}
+
 int fr_backward(const fr_backward_args *a)
 {
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }

@@ -459,6 +459,10 @@ int launch_prune_metric(int P, int kind, const float *contribs, const int32_t *c
 int launch_prune_select(int P, const float *metrics, int64_t k, uint8_t *mask, void *ws, hipStream_t stream);
 int launch_compact_plan(int P, const uint8_t *mask, int invert, int32_t *count_out, void *ws, hipStream_t stream);
 int launch_compact_rows(const fr_compact_args *a, hipStream_t stream);
+size_t densify_workspace_bytes(int P); // densify.hip
+int launch_densify_stats(int P, const float *grad, const uint8_t *filter, float *accum, float *denom, hipStream_t stream);
+int launch_densify_plan(const fr_densify_plan_args *a, hipStream_t stream);
+int launch_densify_rows(const fr_densify_rows_args *a, hipStream_t stream);
 int launch_project(FwdCtx &c); // cull pass + the ordered compaction of its survivors
 int launch_bin(FwdCtx &c);    // projection of the cull pass's survivors, tile counts, colours, item rows
 int launch_tile_scan(FwdCtx &c);

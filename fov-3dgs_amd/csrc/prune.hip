@@ -23,17 +23,15 @@
 //                     kept rows per tile, first destination row of every tile (+ the total), and the gather of every
 //                     tensor of the table in one launch: grid (tiles, tensors)
 #include "common.h"
+#include "row_scan.h"
 
 // the metric must round exactly as written: no contraction, a correctly rounded division
 #pragma clang fp contract(off)
 
 namespace fr {
 
-#define PRUNE_TILE 1024      // rows per tile: 256 threads x 4 consecutive rows (one 16-byte load of metrics, one 4-byte load / store of mask)
-#define PRUNE_PER_THREAD 4
 #define PRUNE_HIST_WGS 256   // most workgroups (= rows of counts) of a histogram pass; the tiles are dealt round-robin
 #define PRUNE_HIST_UNROLL 4  // tiles whose keys a histogram workgroup has in flight at a time
-#define PRUNE_SCAN_CHUNK 256 // tiles k_prune_scan takes per round (one per thread), a carry runs from round to round
 
 struct PruneLayout {
 	size_t bytes;
@@ -64,26 +62,6 @@ __device__ __forceinline__ uint32_t prune_key(float m)
 	if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
 	if ((b & 0x7fffffffu) == 0u) return 0x80000000u;
 	return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// exclusive prefix sum over the 256 threads of a workgroup (s_w: 4 words of LDS); *total gets the sum
-__device__ __forceinline__ uint32_t prune_block_scan(uint32_t v, uint32_t *s_w, uint32_t *total)
-{
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t n = __shfl_up(inc, o);
-		if (lane >= o) inc += n;
-	}
-	if (lane == 63) s_w[w] = inc;
-	__syncthreads();
-	uint32_t pre = 0;
-	for (int k = 0; k < w; k++) pre += s_w[k];
-	*total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-	__syncthreads();
-	return pre + inc - v;
 }
 
 // the keys of rows i .. i + 3 (0 where i + j >= P) and, as the return value, how many of them exist

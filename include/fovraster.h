@@ -423,6 +423,98 @@ typedef struct fr_compact_args {
 int fr_compact_plan(int32_t P, const uint8_t *mask, int32_t invert, int32_t *count_out, void *workspace, void *stream);
 int fr_compact_rows(const fr_compact_args *args, void *stream);
 
+/* Densification: the steps of GaussianModel that add rows (fov3dgs/scene/gaussian_model.py:666-851, :865-867). Every decision
+ * is taken per SOURCE row, so a whole densify_and_prune -- two torch.cat and two prune_points over the full training state in
+ * the reference -- is one plan and one pass over the state. Everything runs on `stream` with no host synchronisation and no
+ * allocation, and every output is one bit pattern, run after run. workspace: fr_densify_workspace_bytes(P) bytes of device
+ * memory, 16-byte aligned; a plan stays valid until the next plan on the same workspace. P = 0 launches nothing.
+ *
+ * Layout of every output tensor (what the reference's cat / [mask] sequence produces):
+ *   kept originals in index order | surviving clones in index order | surviving children of copy 0 in index order | ... of
+ *   copy N - 1.
+ * Child c of the r-th split row (r counted in index order over ALL split rows, surviving or not) reads noise[c * n_split + r]:
+ * the reference's repeat(N, 1) order.
+ *
+ * FR_DENSIFY_AND_PRUNE keeps two quirks of the reference's densify_and_prune (:820-834):
+ *   - densification_postfix zeroes max_radii2D before the final cut (:706), so `max_radii2D > max_screen_size` (:829) is false
+ *     for every non-negative max_screen_size: that argument only switches the world-size test (:830) on (use_world_size);
+ *   - clones carry padded_grad 0 (:734-735) and are small (:807), so they are never split. */
+enum {
+	FR_DENSIFY_CLONE_MASK = 0, /* keep every row; clone where mask is set (position_grad_densify :836-851, any clone)           */
+	FR_DENSIFY_SPLIT_MASK = 1, /* split where mask is set: the parent goes, N children come (:709-729, :757-801)                 */
+	FR_DENSIFY_CLONE_GRAD = 2, /* clone = |g| >= max_grad && smax <= t_dense                      (densify_and_clone, :803-818)  */
+	FR_DENSIFY_SPLIT_GRAD = 3, /* split = g >= max_grad && smax > t_dense                         (densify_and_split, :731-755)  */
+	FR_DENSIFY_AND_PRUNE = 4   /* both, then the opacity / world-size cut                          (densify_and_prune, :820-834)  */
+};
+enum {
+	FR_DENSIFY_COPY = 0,     /* clones and children take the parent's row bitwise                                                */
+	FR_DENSIFY_ZERO_NEW = 1, /* kept originals are copied, every clone or child row is zero (exp_avg, exp_avg_sq: :674-675)       */
+	FR_DENSIFY_XYZ = 2,      /* as COPY, but child c of split row r = (R[0] s0 + R[1] s1) + R[2] s2 + xyz per component, with
+	                            s_k = expf(scaling_k) * noise[c * n_split + r][k] and R = build_rotation(rotation / |rotation|)
+	                            (utils/general_utils.py:78-99); fp32, no contraction                        (:740-744)          */
+	FR_DENSIFY_SCALING = 3   /* as COPY, but children get logf(expf(scaling_k) / (0.8f * N))                       (:745)         */
+};
+size_t fr_densify_workspace_bytes(int32_t P);
+
+/* add_densification_stats (:865-867): for the rows with update_filter != 0
+ *   accum[i] += sqrtf(gx * gx + gy * gy) (the first two columns of grad [P,3], no contraction), denom[i] += 1.   One launch. */
+int fr_densify_stats(int32_t P, const float *grad, const uint8_t *update_filter, float *accum, float *denom, void *stream);
+
+/* The plan (replaces the mask arithmetic of :734-738, :805-807, :821-831 and every .sum() / nonzero of the sequence): one class
+ * byte per source row into the workspace (bit 0 the original is kept, 1 its clone survives, 2 it is split, 3 its children
+ * survive), each tile's first destination row in each of the four segments, and counts_out (a DEVICE int32[4]) = {kept
+ * originals, surviving clones, split rows, surviving children per copy}. With
+ *   g = accum / denom (correctly rounded, NaN -> 0; denom NULL: g = accum; rows >= n_grad: g = 0, the reference's padded_grad),
+ *   smax = max_k expf(scaling_k), o = 1 / (1 + expf(-opacity)), cs_k = logf(expf(scaling_k) / (0.8f * N)):
+ *   clone = |g| >= max_grad && smax <= t_dense           split = g >= max_grad && smax > t_dense
+ *   dead  = o < min_opacity || (use_world_size && smax > t_world)                                   (FR_DENSIFY_AND_PRUNE only)
+ *   kept = !split && !dead, clone survives = clone && !dead,
+ *   children survive = split && !(o < min_opacity || (use_world_size && max_k expf(cs_k) > t_world)) */
+typedef struct fr_densify_plan_args {
+	int32_t P;
+	int32_t mode;           /* FR_DENSIFY_CLONE_MASK .. FR_DENSIFY_AND_PRUNE */
+	int32_t N;              /* children per split row, 1 .. 4 */
+	int32_t use_world_size; /* FR_DENSIFY_AND_PRUNE: max_screen_size was given */
+	int32_t n_grad;         /* the *_GRAD modes: rows of accum (<= P); FR_DENSIFY_AND_PRUNE: P */
+	int32_t reserved;
+	float max_grad, min_opacity;
+	float t_dense;          /* percent_dense * extent */
+	float t_world;          /* 0.1 * extent */
+	const float *accum;     /* [n_grad] xyz_gradient_accum, or the caller's grads with denom = NULL */
+	const float *denom;     /* [n_grad] or NULL */
+	const float *scaling;   /* [P,3] raw _scaling (not read by the *_MASK modes) */
+	const float *opacity;   /* [P] raw _opacity (FR_DENSIFY_AND_PRUNE only) */
+	const uint8_t *mask;    /* [P] the *_MASK modes */
+	int32_t *counts_out;    /* DEVICE int32[4] */
+	void *workspace;
+} fr_densify_plan_args;
+
+typedef struct fr_densify_tensor {
+	const void *src;   /* [P, row_words] words, contiguous */
+	void *dst;         /* [n_keep + n_clone + N * n_child, row_words] words, contiguous */
+	int32_t row_words; /* 4-byte words per row (0: the tensor is skipped); 3 for FR_DENSIFY_XYZ and FR_DENSIFY_SCALING */
+	int32_t role;      /* FR_DENSIFY_COPY .. FR_DENSIFY_SCALING */
+} fr_densify_tensor;
+
+/* The gather (replaces cat_tensors_to_optimizer :666-686, the child arithmetic :740-749 and the _prune_optimizer gathers that
+ * follow): every tensor of the table in ONE launch. n_keep .. n_child are what the plan left in counts_out; a row that would
+ * land beyond its segment is never written. */
+typedef struct fr_densify_rows_args {
+	int32_t P;
+	int32_t N;              /* as given to the plan */
+	int32_t num_tensors;    /* 0 .. FR_COMPACT_MAX_TENSORS */
+	int32_t reserved;
+	int32_t n_keep, n_clone, n_split, n_child;
+	const float *scaling;   /* [P,3] raw _scaling, [P,4] raw _rotation and [N * n_split, 3] standard normal noise: read for the */
+	const float *rotation;  /* children of FR_DENSIFY_XYZ / FR_DENSIFY_SCALING tensors, may be NULL otherwise                    */
+	const float *noise;
+	void *workspace;        /* as given to fr_densify_plan */
+	fr_densify_tensor tensors[FR_COMPACT_MAX_TENSORS];
+} fr_densify_rows_args;
+
+int fr_densify_plan(const fr_densify_plan_args *args, void *stream);
+int fr_densify_rows(const fr_densify_rows_args *args, void *stream);
+
 /* Bytes fr_forward will request for the geometry / image workspaces (P, W, H dependent) and for the
  * binning workspace given a number of instances; lets a caller pre-size persistent buffers. */
 size_t fr_geometry_bytes(int32_t variant, int32_t P);
