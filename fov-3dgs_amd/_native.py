@@ -52,6 +52,11 @@ class ForwardArgs(C.Structure):
     ]
 
 
+class ForwardExt(C.Structure):
+    """fr_forward_ext: optional outputs of fr_forward_begin_ext / fr_forward_ext_call"""
+    _fields_ = [("size", C.c_uint32), ("visibility", _FP)]
+
+
 class BackwardArgs(C.Structure):
     _fields_ = [
         ("variant", C.c_int32), ("P", C.c_int32), ("D", C.c_int32), ("M", C.c_int32), ("R", C.c_int32),
@@ -140,7 +145,11 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_geometry_level_ranges", "fr_forward_begin", "fr_forward_finish", "fr_forward_abandon", "fr_backward_prefill",
            "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step",
            "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows",
-           "fr_densify_workspace_bytes", "fr_densify_stats", "fr_densify_plan", "fr_densify_rows")
+           "fr_densify_workspace_bytes", "fr_densify_stats", "fr_densify_plan", "fr_densify_rows",
+           "fr_forward_begin_ext", "fr_forward_ext_call")
+# added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
+# Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
+OPTIONAL_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
 
 _lib = None
 
@@ -163,7 +172,7 @@ def load():
     except OSError as e:  # missing ROCm runtime, wrong arch, ...
         raise NativeLibraryError(f"fovraster: cannot load {LIB_PATH}: {e}") from e
     for name in EXPORTS:
-        if not hasattr(lib, name):
+        if not hasattr(lib, name) and name not in OPTIONAL_EXPORTS:
             raise NativeLibraryError(f"fovraster: {LIB_PATH} does not export {name}")
     lib.fr_abi_version.restype = C.c_int
     lib.fr_last_error.restype = C.c_char_p
@@ -220,6 +229,11 @@ def load():
     lib.fr_image_tile_levels.restype = C.c_void_p
     lib.fr_forward_begin.argtypes = [C.POINTER(ForwardArgs), C.POINTER(C.c_void_p)]
     lib.fr_forward_begin.restype = C.c_int
+    if has_forward_ext(lib):
+        lib.fr_forward_begin_ext.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(C.c_void_p)]
+        lib.fr_forward_begin_ext.restype = C.c_int
+        lib.fr_forward_ext_call.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt)]
+        lib.fr_forward_ext_call.restype = C.c_int
     lib.fr_forward_finish.argtypes = [C.c_void_p]
     lib.fr_forward_finish.restype = C.c_int
     lib.fr_backward_prefill.argtypes = [C.POINTER(BackwardArgs), C.c_void_p]
@@ -254,6 +268,12 @@ def load():
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib
     return lib
+
+
+def has_forward_ext(lib=None):
+    """the loaded library writes fr_forward_ext.visibility (else: compute it from radii)"""
+    lib = load() if lib is None else lib
+    return all(hasattr(lib, n) for n in OPTIONAL_EXPORTS)
 
 
 def last_error():

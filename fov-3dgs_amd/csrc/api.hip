@@ -220,12 +220,13 @@ struct fr_frame
 
 extern "C" {
 
-int fr_forward_begin(fr_forward_args *a, fr_frame **out)
+int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame **out)
 {
 	if (!out) { set_error("null frame handle"); return FR_ERR_INVALID; }
 	*out = nullptr;
 	int rc = validate_forward(a);
 	if (rc) return rc;
+	if (ext && ext->size < sizeof(fr_forward_ext)) { set_error("fr_forward_ext.size is %u, expected at least %u", ext->size, (unsigned)sizeof(fr_forward_ext)); return FR_ERR_INVALID; }
 	hipStream_t stream = (hipStream_t)a->stream;
 	a->num_rendered = 0;
 	a->max_tile_instances = 0;
@@ -236,6 +237,7 @@ int fr_forward_begin(fr_forward_args *a, fr_frame **out)
 	f->a = a;
 	FwdCtx &c = f->c;
 	c.a = a; c.stream = stream;
+	c.visibility = ext ? ext->visibility : nullptr; // (read here: ext need not outlive this call)
 	if (a->P == 0)
 	{
 		// reference: RasterizeGaussiansCUDA returns the zero-initialised image when P == 0
@@ -256,28 +258,23 @@ int fr_forward_begin(fr_forward_args *a, fr_frame **out)
 	c.geom = carve_geom(a->variant, (size_t)a->P, gptr);
 	c.img = carve_image(a->variant, a->W, a->H, iptr);
 
-	// RF: the two level states of a two-level tile are blended by different waves, which ADD their halves to the image
-	// (clearing only those tiles inside k_tile_levels tripled that kernel: 11 -> 32 us; the fill command is 6 us)
+	// RF: the two level states of a two-level tile are blended by different waves, which ADD their halves to the image: those
+	// tiles' pixels are cleared by k_project's waves beside their stream over the cloud (preprocess.hip). Before that: a fill
+	// command over the whole image on the helper stream, 6 us and a queue slot of its own; clearing only those tiles inside
+	// k_tile_levels tripled that kernel (11 -> 32 us: 45 workgroups cannot write this much).
 	c.fov_split = a->variant == FR_VARIANT_FOV_PCHECK_OBB ? 1 : 0;
 	// The frame's helper stream (s2 of the pair that belongs to this thread and launch stream) carries the large fills -- the
-	// image (RF) and the training variants' two statistics arrays (7 + 6 us at the head of a 1080p foveated frame when they ran in
-	// front of it) -- beside the cull / binning kernels; only the blend kernel at the END of the frame needs them and waits
-	// (fr_forward_finish).
+	// training variants' two statistics arrays -- beside the cull / binning kernels; only the blend kernel at the END of the
+	// frame needs them and waits (fr_forward_finish).
 	f->ax = (!a->debug && !a->no_helper_streams) ? aux_stream(stream) : nullptr;
 	hipStream_t fill_stream = stream;
 	const bool stats = has_stats(a->variant) && !a->no_stats;
-	if (f->ax && (c.fov_split || stats))
+	if (f->ax && stats)
 	{
 		if (hipEventRecord(f->ax->fork, stream) != hipSuccess || hipStreamWaitEvent(f->ax->s2, f->ax->fork, 0) != hipSuccess) { (void)hipGetLastError(); f->ax = nullptr; }
 		else fill_stream = f->ax->s2;
 	}
 	auto fills_done = [&]() { if (fill_stream != stream && hipEventRecord(f->ax->join2, f->ax->s2) == hipSuccess) f->aux_pending = true; };
-	if (c.fov_split)
-	{
-		const hipError_t e = hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)a->W * a->H, fill_stream);
-		fills_done();
-		if (e != hipSuccess) { set_error("hipMemsetAsync(out_color): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-	}
 	if (stats)
 	{
 		const hipError_t e1 = hipMemsetAsync(a->gaussians_count, 0, sizeof(int32_t) * (size_t)a->P, fill_stream);
@@ -409,13 +406,17 @@ int fr_forward_abandon(fr_frame *f)
 	return FR_OK;
 }
 
-int fr_forward(fr_forward_args *a)
+int fr_forward_begin(fr_forward_args *a, fr_frame **out) { return fr_forward_begin_ext(a, nullptr, out); }
+
+int fr_forward_ext_call(fr_forward_args *a, const fr_forward_ext *ext)
 {
 	fr_frame *f = nullptr;
-	const int rc = fr_forward_begin(a, &f);
+	const int rc = fr_forward_begin_ext(a, ext, &f);
 	if (rc) return rc;
 	return fr_forward_finish(f);
 }
+
+int fr_forward(fr_forward_args *a) { return fr_forward_ext_call(a, nullptr); }
 
 int fr_pack_geom(int32_t P, const float *means3D, const float *scales, const float *rotations, const float *opacities,
 	int32_t levels, const float *highest_levels, float *packed_geom, void *stream)

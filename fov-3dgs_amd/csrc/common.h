@@ -419,7 +419,8 @@ struct FwdCtx {
 	fr_forward_args *a;
 	hipStream_t stream;
 	int gx, gy, T;
-	int fov_split;      // RF: the two level states of a two-level tile go to different waves (out_color was zero-filled)
+	int fov_split;      // RF: the two level states of a two-level tile go to different waves (k_project clears those tiles' pixels)
+	uint8_t *visibility; // fr_forward_ext.visibility of the call, or null
 	int bin_wgs;        // workgroups k_bin ran with (k_emit replays the same number)
 	int hist_mode;      // k_bin / k_emit: 0 = global tile counters, 1 = LDS histogram of 32-bit counts, 2 = of 16-bit counts (launch_bin decides)
 	int scan_fused;     // the tile scan ran as the tail of k_bin (launch_bin decides): no k_tile_scan launch

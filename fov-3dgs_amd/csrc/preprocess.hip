@@ -286,6 +286,8 @@ struct PreArgs {
 	int lds_tiles;           // RF: tile_min and the blend flags are staged in LDS (see k_bin)
 	int T;
 	int *radii;
+	uint8_t *visibility;  // [P] 0/1 = radii > 0, written wherever radii is (fr_forward_ext), or null
+	float *clear_color;   // RF: the image, whose two-level tiles k_project clears (see there); null: nothing to clear
 	GeomWS geom;
 	uint32_t *tile_count;
 	uint32_t *hist; // [blocks][T] per-workgroup tile histograms (LDSH)
@@ -668,6 +670,7 @@ __global__ void __launch_bounds__(FR_PROJ_THREADS) k_project(const PreArgs a)
 			else maybe = frame_test<FOV>(a, vm, pm, idx, cur.p, cur.sc, cur.q, cur.hl, wn2, s_lvb);
 			a.radii[idx] = 0; // whole lines (a store with the survivors masked out is a partial-line write); k_bin, which runs
 			                  // after this kernel, writes the radius of every survivor
+			                  // (the visibility bytes of the wave's chunks: cleared in one piece in front of the loop)
 			// auxiliary.h:156-160: the reference traps on a near-culled point of a cloud declared prefiltered
 			if (a.prefiltered && !maybe && (vm[2] * cur.p[0] + vm[6] * cur.p[1] + vm[10] * cur.p[2] + vm[14]) <= 0.2f) atomicOr(a.geom.slab_ctr, 1u);
 		}
@@ -691,8 +694,57 @@ __global__ void __launch_bounds__(FR_PROJ_THREADS) k_project(const PreArgs a)
 #endif
 	// FR_PROJ_DEPTH chunks in flight per wave, each in its own register set that is refilled in place
 	RawGaussian R[DEPTH];
+	// RF: the two level states of a two-level tile ADD their halves to the image (k_render_fov), so those tiles' pixels must hold
+	// zeros by then; every other tile is stored outright. The waves of this kernel share the tiles out -- any grid covers all T --
+	// and clear the flagged ones (the flag the tile scan and the blend go by) beside their stream over the cloud: the stores leave
+	// behind the first chunks' loads and nobody waits for them. (A fill command over the whole image took a launch and 25 MB.)
+	const bool clears = FOV && a.clear_color != nullptr;
+	const float *const tile_bl = a.tile_lv + 4 * (size_t)a.T;
+	float bl = (clears && wave_gid < a.T) ? tile_bl[wave_gid] : 0.0f;
 #pragma unroll
 	for (int d = 0; d < DEPTH; d++) R[d] = fetch(min(c0 + d, nchunks - 1));
+	// the visibility bytes beside the radii this wave zeroes below: the wave's chunks are consecutive, so they are one piece of
+	// memory, cleared here with dword stores (a byte store per chunk inside step() cost the plain instantiations three registers
+	// and with them a wave per SIMD); k_bin, which runs after this kernel, sets the byte of every survivor that keeps its radius
+	if (a.visibility && c0 < c1)
+	{
+		const int b0 = c0 * 64, b1 = min(a.P, c1 * 64);
+		if (((uintptr_t)a.visibility & 3) == 0)
+		{
+			for (int i = b0 + 4 * lane; i + 3 < b1; i += 256) *(uint32_t *)(a.visibility + i) = 0u;
+			const int t = b0 + ((b1 - b0) & ~3); // (P is no multiple of four: the last wave's last bytes)
+			if (t + lane < b1) a.visibility[t + lane] = 0;
+		}
+		else
+			for (int i = b0 + lane; i < b1; i += 64) a.visibility[i] = 0;
+	}
+	if (clears)
+	{
+		static_assert(FR_TILE == 16, "a wave clears a tile plane as 16 rows of four lanes");
+		const size_t plane = (size_t)a.W * a.H;
+		const int ly = lane >> 2, lx = (lane & 3) * 4;
+		const bool vec = (a.W & 3) == 0 && ((uintptr_t)a.clear_color & 15) == 0; // (then every row piece is a whole, aligned float4)
+		for (int tile = wave_gid; tile < a.T; )
+		{
+			const int x = (tile % a.gx) * FR_TILE + lx, y = (tile / a.gx) * FR_TILE + ly;
+			if (bl != 0.0f && y < a.H)
+			{
+				float *dst = a.clear_color + (size_t)a.W * y + x;
+#pragma unroll
+				for (int ch = 0; ch < 3; ch++, dst += plane)
+				{
+					if (vec) { if (x < a.W) *(float4 *)dst = make_float4(0.f, 0.f, 0.f, 0.f); }
+					else
+					{
+#pragma unroll
+						for (int k = 0; k < 4; k++) if (x + k < a.W) dst[k] = 0.0f;
+					}
+				}
+			}
+			tile += nwaves;
+			bl = tile < a.T ? tile_bl[tile] : 0.0f;
+		}
+	}
 	for (int base = c0; base < c1; base += DEPTH)
 	{
 #pragma unroll
@@ -1211,6 +1263,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		if (valid)
 		{
 			a.radii[gidx] = go.alive ? go.radius : 0;
+			if (a.visibility) a.visibility[gidx] = (go.alive && go.radius > 0) ? 1 : 0;
 			a.geom.vis_list[item] = (uint32_t)gidx;
 		}
 		rows_store<4>(go.wrow, orec, a.geom.wrec + 4 * (size_t)slab * 64, nv, lane);
@@ -1368,7 +1421,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	// tiles were all rejected lose their radius (RS rasterizer_impl.cu:141-145)
 	const uint32_t lr = (alive && !deferred) ? range_word(count, lowest, highest, be_blend) : FR_ITEM_NONE;
 	if (item < V && !deferred) a.geom.lrange[item] = lr;
-	if (alive && !deferred && count == 0) a.radii[idx] = 0;
+	if (alive && !deferred && count == 0) { a.radii[idx] = 0; if (a.visibility) a.visibility[idx] = 0; }
 	// ---- the colours of the slab's items that landed in a tile; the blend record leaves with them (RF: the level rows) ----
 	if (__any(lr != FR_ITEM_NONE))
 	{
@@ -1409,7 +1462,12 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		if (FOV && gcount != 0) range_from_mask(s_gmask[threadIdx.x], lowest, highest, be_blend);
 		const uint32_t lr = range_word(gcount, lowest, highest, be_blend);
 		a.geom.lrange[gitem] = lr;
-		if (gcount == 0) a.radii[__float_as_uint(w2.x) & 0x3fffffffu] = 0;
+		if (gcount == 0)
+		{
+			const uint32_t gi = __float_as_uint(w2.x) & 0x3fffffffu;
+			a.radii[gi] = 0;
+			if (a.visibility) a.visibility[gi] = 0;
+		}
 		else
 		{
 			float4 r[3], lv[FR_FOV_LEVELS];
@@ -1897,7 +1955,7 @@ static PreArgs make_pre_args(FwdCtx &c)
 	p.viewmatrix = a->viewmatrix; p.projmatrix = a->projmatrix; p.campos = a->campos;
 	p.packed_geom = a->packed_geom; p.packed_colour = a->packed_colour; p.packed_cull = a->packed_cull;
 	p.shs_dcs = a->shs_dcs; p.highest_levels = a->highest_levels; p.tile_lv = c.img.tile_lv; p.lv_bbox = c.img.lv_bbox; p.T = c.T;
-	p.radii = a->radii; p.geom = c.geom; p.tile_count = c.img.tile_count; p.hist = c.img.hist; p.raw = a->raw_activations;
+	p.radii = a->radii; p.visibility = c.visibility; p.clear_color = c.fov_split ? a->out_color : nullptr; p.geom = c.geom; p.tile_count = c.img.tile_count; p.hist = c.img.hist; p.raw = a->raw_activations;
 	p.write_cov3D = has_backward(a->variant) ? 1 : 0;
 	p.prefiltered = a->prefiltered;
 	p.proj_waves = c.proj_waves; p.proj_cpw = c.proj_cpw;

@@ -191,7 +191,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     if ender is not None:
         ender.record()
 
-    result = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0,
+    visible = getattr(out, "visibility_filter", None)  # (written beside the radii by the kernels, rasterizer.RasterOutput)
+    result = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": visible if visible is not None else out[1] > 0,
               "radii": out[1]}
     if len(out) == 4:
         result["gs_count"], result["contribs"] = out[2], out[3]

@@ -7,7 +7,7 @@ import torch
 
 from ..diff_gaussian_rasterization_fov_pcheck_obb import GaussianRasterizationSettings, GaussianRasterizer
 from .. import _native
-from ..rasterizer import PackedModel, _forward_begin, pack_model, serial_frames, zero_points_like
+from ..rasterizer import PackedModel, _forward_begin, pack_model, serial_frames, visibility_of, zero_points_like
 
 
 class _PackState:
@@ -116,7 +116,8 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
     if ender is not None:
         ender.record()
 
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+    # (`radii > 0` as the kernels that write the radii left it: no pass of torch's over the radii behind the frame)
+    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visibility_of(radii),
             "radii": radii}
 
 
@@ -130,8 +131,11 @@ class PendingRender:
         frame = self._frame
         res = frame.finish()
         radii = res[2]
-        with torch.cuda.device(frame.device), torch.cuda.stream(frame.stream):  # `radii` is written on the frame's stream
-            visible = radii > 0
+        if getattr(radii, "_fovraster_visibility", None) is not None:
+            visible = visibility_of(radii)  # written beside `radii`, on the frame's stream
+        else:
+            with torch.cuda.device(frame.device), torch.cuda.stream(frame.stream):  # `radii` is written on the frame's stream
+                visible = radii > 0
         return {"render": res[1], "viewspace_points": self._points, "visibility_filter": visible, "radii": radii}
 
 

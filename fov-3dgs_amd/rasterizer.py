@@ -311,6 +311,36 @@ _call_events = None  # profiling.NativeCallTimer: a list that takes (kind, start
 _bwd_events_hook = None  # the same for backward calls: 5 handles (fr_backward_args.stage_events)
 
 
+class RasterOutput(tuple):
+    """What GaussianRasterizer.__call__ returns: the reference's tuple -- (color, radii[, gaussians_count, contributions]) --
+    with one attribute beside it: visibility_filter, the [P] bool tensor `radii > 0` as the kernels that write the radii wrote
+    it (fr_forward_ext.visibility), or None when the loaded library does not write it (the renderers then compute it)."""
+    visibility_filter = None
+
+
+def _raster_output(out):
+    res = RasterOutput(out)
+    res.visibility_filter = getattr(out[1], "_fovraster_visibility", None)
+    return res
+
+
+def visibility_of(radii):
+    """`radii > 0` of a radii tensor of this module: the mask the native call wrote beside it, else computed"""
+    vis = getattr(radii, "_fovraster_visibility", None)
+    return vis if vis is not None else radii > 0
+
+
+def _begin_call(lib, a, P, dev, radii, handle):
+    """fr_forward_begin with the visibility mask as a second output where the library has it: the mask travels as an attribute of
+    `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object)."""
+    if not _native.has_forward_ext(lib):
+        return lib.fr_forward_begin(C.byref(a), C.byref(handle))
+    vis = torch.empty((P,), dtype=torch.bool, device=dev)  # written in full beside radii, like it
+    radii._fovraster_visibility = vis
+    ext = _native.ForwardExt(C.sizeof(_native.ForwardExt), vis.data_ptr())  # (read during the call only)
+    return lib.fr_forward_begin_ext(C.byref(a), C.byref(ext), C.byref(handle))
+
+
 class FrameInFlight:
     """A forward call between its two halves (fr_forward_begin / fr_forward_finish, include/fovraster.h): the head of the
     frame is on the stream, finish() waits for the instance count and enqueues the rest. Holds everything the native call
@@ -378,7 +408,7 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         a.out_color, a.radii = color.data_ptr(), radii.data_ptr()
         a.stage_events = _stage_events_hook() if _stage_events_hook is not None else None
         handle = C.c_void_p()
-        rc = lib.fr_forward_begin(C.byref(a), C.byref(handle))
+        rc = _begin_call(lib, a, P, dev, radii, handle)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
         return FrameInFlight(lib, a, keep, color, radii, ws, None, None, None, handle, dev, stream)
@@ -466,7 +496,7 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if _stage_events_hook is not None:
             a.stage_events = _stage_events_hook()
         handle = C.c_void_p()
-        rc = lib.fr_forward_begin(C.byref(a), C.byref(handle))
+        rc = _begin_call(lib, a, P, dev, radii, handle)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
     if reuse is not None:
@@ -604,7 +634,7 @@ def _forward_overlapped(args, kw):
             done.record(own)
     st.done[i] = done
     cur.wait_event(done)  # everything the caller enqueues from here on sees the finished frame
-    for t in res:
+    for t in res + (getattr(res[2], "_fovraster_visibility", None),):
         if isinstance(t, torch.Tensor) and t.is_cuda:
             t.record_stream(cur)
     return res
@@ -1012,8 +1042,8 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             scales = empty if scales is None else scales
             rotations = empty if rotations is None else rotations
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, raster_settings, loss_map, shs_rest, packed, raw_activations, row_sparse, want_stats)
+            return _raster_output(rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, raster_settings, loss_map, shs_rest, packed, raw_activations, row_sparse, want_stats))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 
@@ -1096,9 +1126,9 @@ def _make_fov():
             scales = empty if scales is None else scales
             rotations = empty if rotations is None else rotations
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-            return rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
+            return _raster_output(rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                       blending, packed)
+                                       blending, packed))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 
@@ -1163,8 +1193,8 @@ def _make_naive_fov():
             scales = empty if scales is None else scales
             rotations = empty if rotations is None else rotations
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, raster_settings, highest_levels, gazeArray, alpha, blending)
+            return _raster_output(rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, raster_settings, highest_levels, gazeArray, alpha, blending))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 
@@ -1244,7 +1274,7 @@ def _make_mmfr():
             scales = empty if scales is None else scales
             rotations = empty if rotations is None else rotations
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, raster_settings, cur_level, gazeArray, alpha, blending)
+            return _raster_output(rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, raster_settings, cur_level, gazeArray, alpha, blending))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer

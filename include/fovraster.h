@@ -110,7 +110,9 @@ typedef struct fr_forward_args {
 	const float *campos;         /* [3] */
 	const float *shs_dcs;        /* RF: [P,4,3] per-level DC coefficient */
 	const float *highest_levels; /* RF: [P,1] float */
-	/* outputs (caller-allocated; out_color and radii are written in full, they need no initialisation) */
+	/* outputs (caller-allocated; out_color and radii are written in full, they need no initialisation: every pixel by the
+	 * blend -- RF: the two-level tiles, whose two level states are ADDED, are cleared by the cull pass first; no fill command
+	 * touches the image --, every radius by the cull pass or the projection) */
 	float *out_color;            /* [3,H,W] */
 	int32_t *radii;              /* [P] */
 	int32_t *gaussians_count;    /* RS: [P], else NULL (zeroed by the call, then accumulated) */
@@ -259,7 +261,7 @@ int fr_event_elapsed_ms(void *start, void *stop, float *ms); /* synchronises on 
 
 int fr_forward(fr_forward_args *args);
 /* The same call in two halves (fr_forward == begin, then finish):
- *   fr_forward_begin   validates, asks for the geometry and image workspaces, enqueues the head of the frame (fills, tile levels,
+ *   fr_forward_begin   validates, asks for the geometry and image workspaces, enqueues the head of the frame (small fills, tile levels,
  *                      cull pass, projection, tile counts, tile scan) and returns without waiting for anything; *frame is
  *                      the handle of the frame in flight (NULL on error). `args` must stay alive and unchanged until
  *                      fr_forward_finish(*frame) has returned, which must be called exactly once, by the same host thread.
@@ -275,6 +277,17 @@ int fr_forward_finish(fr_frame *frame);
  * joins the frame's helper stream into its launch stream, releases the pinned totals block and the handle; no wait, no callback,
  * no launch. out_color is left undefined. */
 int fr_forward_abandon(fr_frame *frame);
+/* Optional outputs beside fr_forward_args (whose layout FR_ABI_VERSION pins). size = sizeof(fr_forward_ext) as the caller was
+ * compiled; the struct is read during the call only.
+ *   visibility  [P] bytes, or NULL: 1 where radii > 0, else 0 -- written in full by the kernels that write radii (no initialisation
+ *               needed), so a host that wants the reference's `radii > 0` mask needs no pass of its own over radii.
+ * fr_forward_begin_ext / fr_forward_ext_call are fr_forward_begin / fr_forward with these outputs; ext == NULL: the same calls. */
+typedef struct fr_forward_ext {
+	uint32_t size;
+	uint8_t *visibility;
+} fr_forward_ext;
+int fr_forward_begin_ext(fr_forward_args *args, const fr_forward_ext *ext, fr_frame **frame);
+int fr_forward_ext_call(fr_forward_args *args, const fr_forward_ext *ext);
 /* Fill fr_forward_args.packed_geom / packed_colour / packed_cull (device buffers of P*16 / P*64 / P*4 floats) from the tensors of the
  * same names; opacities is [P,levels] with levels = 1 or 4, highest_levels / shs_dcs may be NULL (not RF);
  * shs_rest NULL: shs is [P,16,3] (RF: [P,15,3] = coefficients 1..15 and shs_dcs given), else shs = [P,1,3]. */
