@@ -146,7 +146,7 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step",
            "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows",
            "fr_densify_workspace_bytes", "fr_densify_stats", "fr_densify_plan", "fr_densify_rows",
-           "fr_forward_begin_ext", "fr_forward_ext_call")
+           "fr_forward_begin_ext", "fr_forward_ext_call", "fr_backward_appearance")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 OPTIONAL_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -185,6 +185,8 @@ def load():
     lib.fr_forward.restype = C.c_int
     lib.fr_backward.argtypes = [C.POINTER(BackwardArgs)]
     lib.fr_backward.restype = C.c_int
+    lib.fr_backward_appearance.argtypes = [C.POINTER(BackwardArgs)]
+    lib.fr_backward_appearance.restype = C.c_int
     lib.fr_mark_visible.argtypes = [C.c_int32, _FP, _FP, _FP, _FP, C.c_void_p]
     lib.fr_mark_visible.restype = C.c_int
     lib.fr_pack_geom.argtypes = [C.c_int32, _FP, _FP, _FP, _FP, C.c_int32, _FP, _FP, C.c_void_p]

@@ -645,6 +645,25 @@ int fr_backward(const fr_backward_args *a)
 	return launch_backward(a);
 }
 
+int fr_backward_appearance(const fr_backward_args *a)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (!has_backward(a->variant))
+	{ set_error("backward exists only for the original and pcheck_obb_sum/_max/_loss_weighted_max_count variants (the reference's inference variants have none)"); return FR_ERR_INVALID; }
+	// only the opacity and the colour are differentiated: a pointer for anything else would stay unwritten, so it is refused
+	const struct { const void *p; const char *name; } forbidden[] = {
+		{ a->dL_dmean2D, "dL_dmean2D" }, { a->dL_dconic, "dL_dconic" }, { a->dL_dmean3D, "dL_dmean3D" }, { a->dL_dcov3D, "dL_dcov3D" },
+		{ a->dL_dscale, "dL_dscale" }, { a->dL_drot, "dL_drot" }, { a->dL_dsh_rest, "dL_dsh_rest" } };
+	for (const auto &f : forbidden)
+		if (f.p) { set_error("backward_appearance: %s must be NULL (only dL_dopacity, dL_dsh = the DC part and dL_dcolor are written)", f.name); return FR_ERR_INVALID; }
+	if (a->P == 0) return FR_OK;
+	if (!a->geometry || !a->image || (a->R > 0 && !a->binning) || !a->dL_dpix || !a->background) { set_error("missing workspace / gradient pointer"); return FR_ERR_INVALID; }
+	if (!a->dL_dopacity) { set_error("backward_appearance: dL_dopacity is null"); return FR_ERR_INVALID; }
+	if (a->dL_dsh && (!a->shs || a->colors_precomp)) { set_error("backward_appearance: dL_dsh needs shs (with colors_precomp ask for dL_dcolor)"); return FR_ERR_INVALID; }
+	if (a->raw_activations && a->cov3D_precomp) { set_error("raw_activations needs scales + rotations"); return FR_ERR_INVALID; }
+	return launch_backward_appearance(a);
+}
+
 int fr_backward_prefill(const fr_backward_args *a, void *fill_stream)
 {
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }

@@ -76,6 +76,24 @@ __device__ __forceinline__ float fold18(const float (&a)[9], const float (&b)[9]
 	return last ? z : m;
 }
 
+// The FOUR sums of the appearance-only pass (colour r g b and M00: what the gradients of the opacity and of the DC colour are linear
+// in) of TWO list entries: eight values fill fold32 -> fold16 -> row_sum16 exactly. Afterwards row r of 16 lanes holds entry r >> 1's
+// value (r & 1) in t0 and its value 2 + (r & 1) in t1: two lanes of every row write, eight lanes with one atomic instruction.
+// 8 + 4 + 8 = 20 instructions for two entries (the four-entry shape: 16 + 8 for the swaps, then 4 + 2 + 2 + 1 + 2 as in fold18 = 35
+// for four, but three selects more for the writers' rows and twelve waiting registers: no fewer per entry once those are counted).
+// -> the lane's total (valid where `writer`), whose it is (entry 0 / 1) and its component (0, 1, 2 or 8) of the gradient-sum row
+__device__ __forceinline__ float fold8(const float (&a)[4], const float (&b)[4], const int lane, int &entry, int &comp, bool &writer)
+{
+	const float f0 = fold32(a[0], b[0]), f1 = fold32(a[1], b[1]), f2 = fold32(a[2], b[2]), f3 = fold32(a[3], b[3]);
+	const float t0 = row_sum16(fold16(f0, f1)), t1 = row_sum16(fold16(f2, f3));
+	const int r = lane >> 4, sel = lane & 15;
+	const int k = 2 * sel + (r & 1);
+	entry = r >> 1;
+	comp = k == 3 ? 8 : k;
+	writer = sel < 2;
+	return sel ? t1 : t0;
+}
+
 struct BwdRenderArgs {
 	int W, H, gx;
 	const uint2 *ranges;
@@ -91,10 +109,14 @@ struct BwdRenderArgs {
 	uint32_t *pairs; // optional diagnostic (fr_backward_args.blend_pairs): [T], (band, entry) pairs evaluated, or null
 };
 
-template <bool CUTOFF>
+// LEAN (fr_backward_appearance): only the colour sums and M00 are formed and folded (fold8), into the same components of the row
+// (0, 1, 2 and 8); the five other moments and the products that serve only them are left out. Walk, staging, skip tests and the
+// recovery of T are the same code.
+template <bool CUTOFF, bool LEAN = false>
 __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 {
 	constexpr int PPL = 2;
+	constexpr int NV = LEAN ? 4 : 9; // sums per (band, entry) pair
 	__shared__ float4 s0[64];  // x, y, conic a, conic b
 	__shared__ float4 s1[64];  // conic c, opacity, r, g
 	__shared__ float4 s2[64];  // b, row of the gradient sums (int bits), tq (the forward blend's threshold on q = -power), -
@@ -159,7 +181,7 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 	if (lane < wave_last) fetch(wave_last - 1 - lane);
 	uint32_t npairs = 0;
 	// an entry's nine sums wait for the next entry's: two entries are folded together (fold18)
-	float pend[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	float pend[NV] = {};
 	int pend_row = 0;
 	bool have_pend = false;
 	auto fold_one = [&](const float (&v)[9], const int row) __attribute__((always_inline))
@@ -222,7 +244,7 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 			const bool on_x = pos < lastc[0] && __float_as_uint(q.x) <= tqb; // 0 <= q <= tq: in the support and alpha >= 1/255
 			const bool on_y = pos < lastc[1] && __float_as_uint(q.y) <= tqb;
 			const bool any = on_x || on_y;
-			float v[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }; // colour r g b, moments M10 M01 M20 M11 M02 M00 of G dL/dalpha
+			float v[NV] = {}; // colour r g b, moments M10 M01 M20 M11 M02 M00 of G dL/dalpha (LEAN: r g b, M00)
 			if (__any(any))
 			{
 				// A pixel that is not `on` takes part with alpha = 0 and G = 0: 1 / (1 - 0) = 1 leaves its transmittance, 0 c + 1 A its
@@ -258,12 +280,16 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 				// M20 = dx M10, M11 = dx M01): three packed products and three plain ones where six packed products were
 				const bv2 w = Gm * dA;
 				const float m00 = hsum(w);
-				const float m10 = m00 * dx, m20 = m10 * dx;
-				const bv2 wy = w * dy;
-				const float m01 = hsum(wy);
-				const float m11 = m01 * dx;
-				const float m02 = fmaf(wy.y, dy.y, wy.x * dy.x);
-				v[3] = m10; v[4] = m01; v[5] = m20; v[6] = m11; v[7] = m02; v[8] = m00;
+				if constexpr (LEAN) v[3] = m00;
+				else
+				{
+					const float m10 = m00 * dx, m20 = m10 * dx;
+					const bv2 wy = w * dy;
+					const float m01 = hsum(wy);
+					const float m11 = m01 * dx;
+					const float m02 = fmaf(wy.y, dy.y, wy.x * dy.x);
+					v[3] = m10; v[4] = m01; v[5] = m20; v[6] = m11; v[7] = m02; v[8] = m00;
+				}
 			}
 			if (__any(any))
 			{
@@ -271,20 +297,32 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 				if (!have_pend)
 				{
 			#pragma unroll
-					for (int i = 0; i < 9; i++) pend[i] = v[i];
+					for (int i = 0; i < NV; i++) pend[i] = v[i];
 					pend_row = row; have_pend = true;
 				}
 				else
 				{
 					int e, comp; bool writer;
-					const float val = fold18(pend, v, lane, e, comp, writer);
-					if (writer) atomicAdd(a.acc + 16 * (size_t)(e ? row : pend_row) + comp, val); // eighteen lanes, two cache lines
+					float val;
+					if constexpr (LEAN) val = fold8(pend, v, lane, e, comp, writer);
+					else val = fold18(pend, v, lane, e, comp, writer);
+					if (writer) atomicAdd(a.acc + 16 * (size_t)(e ? row : pend_row) + comp, val); // eighteen (LEAN: eight) lanes, two cache lines
 					have_pend = false;
 				}
 			}
 		}
 	}
-	if (have_pend) fold_one(pend, pend_row); // an odd entry is left
+	if constexpr (LEAN)
+	{
+		if (have_pend) // an odd entry is left: folded with zeros, the first entry's four lanes write
+		{
+			const float none[NV] = {};
+			int e, comp; bool writer;
+			const float val = fold8(pend, none, lane, e, comp, writer);
+			if (writer && e == 0) atomicAdd(a.acc + 16 * (size_t)pend_row + comp, val);
+		}
+	}
+	else if (have_pend) fold_one(pend, pend_row); // an odd entry is left
 	if (a.pairs != nullptr && lane == 0 && npairs != 0) atomicAdd(a.pairs + tile, npairs);
 }
 
@@ -871,7 +909,53 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(const BwdPreArgs a)
 	}
 }
 
-static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, const ImageWS &img, const BinWS &bin, int gx, int T, hipStream_t stream)
+// ---- appearance-only per-Gaussian pass (fr_backward_appearance) ---------------------------------------------------------------
+// What the mask-learning step differentiates (gaussian_renderer/__init__.py:71-82 detaches everything else): per visible-list item
+// the four sums of the lean tile pass and two words of its blend record (opacity, clamp bits) become
+//   dL/dopacity = M00 (through the sigmoid, o (1 - o), for the raw parameter),
+//   dL/dDC      = SH_C0 * colour sums, zero for a channel the forward pass clamped (backward.cu:20-139),
+//   dL/dcolour  = the colour sums (optional):
+// 16 bytes a row, no coefficient rows, no chain rule, nothing of the model read. The components read (0, 1, 2 and 8 of the row) are
+// cleared again (the idempotence contract of fr_backward_args.geometry; the others are zero between calls and are not touched,
+// the last quarter is the forward pass's). Items that landed in no tile are skipped (dense outputs: their zeros are the fill's) or
+// get a zero row (row_sparse: every row is written).
+struct BwdAppArgs {
+	const float4 *rec;
+	float *acc;                // [V][16]
+	float *dL_dopacity, *dL_dsh, *dL_dcolor; // [., 1], [., 1, 3] or null, [., 3] or null
+	const uint32_t *vis_list, *vis_count, *lrange;
+	int raw, row_sparse;
+};
+
+__global__ void __launch_bounds__(256) k_appearance_bwd(const BwdAppArgs a)
+{
+	const int V = (int)*a.vis_count;
+	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x))
+	{
+		const bool alive = a.lrange[i] != FR_ITEM_NONE;
+		if (!alive && !a.row_sparse) continue;
+		const size_t orow = a.row_sparse ? (size_t)i : (size_t)a.vis_list[i];
+		float g_op = 0.0f, gc[3] = { 0.f, 0.f, 0.f }, gd[3] = { 0.f, 0.f, 0.f };
+		if (alive)
+		{
+			float *row = a.acc + 16 * (size_t)i;
+			gc[0] = row[0]; gc[1] = row[1]; gc[2] = row[2];
+			const float m00 = row[8];
+			row[0] = 0.0f; row[1] = 0.0f; row[2] = 0.0f; row[8] = 0.0f;
+			const float opac = a.rec[3 * (size_t)i + 1].y;
+			const uint32_t clamp_bits = __float_as_uint(a.rec[3 * (size_t)i + 2].z);
+			g_op = a.raw ? m00 * opac * (1.0f - opac) : m00;
+#pragma unroll
+			for (int ch = 0; ch < 3; ch++) gd[ch] = FR_SH_C0 * ((clamp_bits >> ch) & 1u ? 0.0f : gc[ch]);
+		}
+		FR_ST(a.dL_dopacity + orow, g_op);
+		if (a.dL_dsh != nullptr) { FR_ST(a.dL_dsh + 3 * orow, gd[0]); FR_ST(a.dL_dsh + 3 * orow + 1, gd[1]); FR_ST(a.dL_dsh + 3 * orow + 2, gd[2]); }
+		if (a.dL_dcolor != nullptr) { FR_ST(a.dL_dcolor + 3 * orow, gc[0]); FR_ST(a.dL_dcolor + 3 * orow + 1, gc[1]); FR_ST(a.dL_dcolor + 3 * orow + 2, gc[2]); }
+	}
+}
+
+static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, const ImageWS &img, const BinWS &bin, int gx, int T, hipStream_t stream,
+	bool lean = false)
 {
 	BwdRenderArgs r;
 	r.W = a->W; r.H = a->H; r.gx = gx; r.ranges = img.ranges; r.render_items = img.render_items; r.n_items = 2u * (uint32_t)T;
@@ -883,6 +967,14 @@ static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, cons
 	{
 		const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
 		if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+	}
+	if (lean)
+	{
+		if (a->variant == FR_VARIANT_ORIGINAL)
+			hipLaunchKernelGGL((k_render_bwd<false, true>), dim3(r.n_items), dim3(64), 0, stream, r);
+		else
+			hipLaunchKernelGGL((k_render_bwd<true, true>), dim3(r.n_items), dim3(64), 0, stream, r);
+		return check_launch("render_bwd (appearance)", stream, a->debug);
 	}
 	if (a->variant == FR_VARIANT_ORIGINAL)
 		hipLaunchKernelGGL((k_render_bwd<false>), dim3(r.n_items), dim3(64), 0, stream, r);
@@ -1051,6 +1143,65 @@ int launch_backward(const fr_backward_args *a)
 		// row is complete behind this launch (the rows of a row-sparse call are not Gaussian indices: no call)
 		if (!rc2 && a->range_done != nullptr && !a->row_sparse) a->range_done(a->range_user, 0, 0, a->P);
 	}
+	mark(2);
+	return rc2;
+}
+
+// fr_backward_appearance. The dense outputs are 16 bytes a Gaussian (96 MB at 6 M where the full pass clears 1.5 GB): ONE k_fill_zero
+// over them on the caller's stream in front of the tile pass, then the visible rows stored one by one -- chosen for simplicity over
+// the whole-line scheme (SmallSet) and over a helper stream: no second stream, no radii, nothing to join.
+int launch_backward_appearance(const fr_backward_args *a)
+{
+	hipStream_t stream = (hipStream_t)a->stream;
+	const int gx = (a->W + FR_TILE - 1) / FR_TILE, gy = (a->H + FR_TILE - 1) / FR_TILE, T = gx * gy;
+	GeomWS geom = carve_geom(a->variant, (size_t)a->P, (char *)a->geometry);
+	ImageWS img = carve_image(a->variant, a->W, a->H, (char *)a->image);
+	BinWS bin = carve_bin(a->R, (char *)a->binning);
+	auto mark = [&](int i) { if (a->stage_events && a->stage_events[i]) (void)hipEventRecord((hipEvent_t)a->stage_events[i], stream); };
+	if (!a->row_sparse && !a->outputs_zeroed)
+	{
+		const size_t P = (size_t)a->P;
+		struct { void *p; size_t words; } fills[] = { { a->dL_dopacity, P }, { a->dL_dsh, 3 * P }, { a->dL_dcolor, 3 * P } };
+		FillArgs fa; fa.n = 0;
+		mark(3);
+		for (auto &f : fills)
+			if (f.p)
+			{
+				if (((uintptr_t)f.p & 15) != 0)
+				{
+					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
+					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+					continue;
+				}
+				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
+			}
+		if (fa.n)
+		{
+			const size_t quads = (3 * P + 3) / 4;
+			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
+			hipLaunchKernelGGL(k_fill_zero, dim3(blocks), dim3(256), 0, stream, fa);
+			const int rcf = check_launch("fill_zero (appearance)", stream, a->debug);
+			if (rcf) return rcf;
+		}
+		mark(4);
+	}
+	mark(0);
+	if (a->R > 0)
+	{
+		const int rc0 = launch_render_bwd(a, geom, img, bin, gx, T, stream, true);
+		if (rc0) return rc0;
+	}
+	mark(1);
+	BwdAppArgs p;
+	p.rec = geom.rec; p.acc = (float *)geom.acc;
+	p.dL_dopacity = a->dL_dopacity; p.dL_dsh = a->dL_dsh; p.dL_dcolor = a->dL_dcolor;
+	p.vis_list = geom.vis_list; p.vis_count = geom.slab_ctr + 1; p.lrange = geom.lrange;
+	p.raw = a->raw_activations; p.row_sparse = a->row_sparse;
+	const int pblocks = (a->P + 255) / 256;
+	hipLaunchKernelGGL(k_appearance_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
+	const int rc2 = check_launch("appearance_bwd", stream, a->debug);
+	// one piece: every row of the dense outputs is complete behind this launch (fovraster.h: the single-piece rule of range_done)
+	if (!rc2 && a->range_done != nullptr && !a->row_sparse) a->range_done(a->range_user, 0, 0, a->P);
 	mark(2);
 	return rc2;
 }

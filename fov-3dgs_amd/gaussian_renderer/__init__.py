@@ -6,6 +6,7 @@ active_sh_degree), `viewpoint_camera` anything with the Camera/MiniCam fields.
 """
 import inspect
 import math
+import warnings
 
 import torch
 
@@ -43,6 +44,7 @@ _REFERENCE_GETTERS = {
 }
 _class_verdict = {}   # class -> bool: fingerprints ok (None entry never stored)
 _class_checked = {}   # class -> bool: numeric self-check passed
+_warned_no_split = False
 
 
 def _getter_fingerprint_ok(cls):
@@ -107,15 +109,25 @@ def _reference_model_fields(pc):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, masking=False,
-           starter=None, ender=None, cuda_type="", loss_map=None, packed=None, want_stats=True):
+           starter=None, ender=None, cuda_type="", loss_map=None, packed=None, want_stats=True, appearance_only=False):
     """Render the scene. Background tensor (bg_color) must be on the GPU.
     packed (extension): a rasterizer.PackedModel of this (static) model made by pack_model(); same image, faster binning.
     want_stats (extension, opt-in): False = the caller does not read result["gs_count"] / ["contribs"] of the pcheck_obb_sum
     rasterizer (eff_finetune.py:107-108 drops them every step): the blend skips the per-Gaussian statistics and the two keys
-    are absent from the result; image, radii and gradients are unchanged."""
+    are absent from the result; image, radii and gradients are unchanged.
+    appearance_only (extension, opt-in, with masking=True: the mask-learning step, metric_mask_learn.py:213): masking detaches
+    positions, scales, rotations and the rest SH coefficients (reference gaussian_renderer/__init__.py:71-82), so the backward pass
+    computes the gradients of the opacity and of the DC colour and nothing else (fr_backward_appearance). Same image, same two
+    gradients; result["viewspace_points"] is a plain zero tensor without grad (nothing in the mask loop reads it). The raw-parameter
+    and reference-model fast paths, which masking otherwise rules out, are taken again: the gradient arrives at the raw _opacity.
+    A model that only offers the concatenated get_features_detach_rest is rendered as without the flag (one warning)."""
+    if appearance_only and not masking:
+        raise ValueError("appearance_only is the backward pass of the masking step: call render(..., masking=True, appearance_only=True)")
     xyz = pc.get_xyz
     # zero tensor that makes autograd return the gradient of the 2D (screen-space) means
-    if torch.is_grad_enabled():
+    if appearance_only:
+        screenspace_points = zero_points_like(xyz)
+    elif torch.is_grad_enabled():
         screenspace_points = zero_points_leaf(xyz)
         try:
             screenspace_points.retain_grad()
@@ -147,10 +159,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     # extensions of this package, picked up when the model offers them: the RAW parameters (the rasterizer applies exp /
     # normalize / sigmoid itself and returns the gradients w.r.t. them: no pass over all P Gaussians on either side of
     # the step); else the three activations as one fused pass (activations.py); else the reference's three getters
-    raw = getattr(pc, "get_raw_activation_params", None) if (packed is None and not masking) else None
+    # (masking detaches scales and rotations, whose raw-parameter gradients fr_backward would compute for nothing: no raw parameters
+    # then -- unless the backward pass is the appearance-only one, which computes neither)
+    allow_raw = packed is None and (not masking or appearance_only)
+    raw = getattr(pc, "get_raw_activation_params", None) if allow_raw else None
     act = getattr(pc, "get_activated", None) if raw is None else None
     ref_fields = _reference_model_fields(pc) if (raw is None and act is None and not hasattr(pc, "get_features_split")) else None
-    if ref_fields is not None and packed is None and not masking:
+    if ref_fields is not None and allow_raw:
         raw = ref_fields[:3]
     if raw is not None:
         scales, rotations, opacity = raw
@@ -180,6 +195,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     # i.e. with the raw parameters and split SH storage)
     if not want_stats and cuda_type == "pcheck_obb_sum":
         extra["want_stats"] = False
+    if appearance_only:
+        if isinstance(shs, tuple):
+            extra["appearance_only"] = True
+        else:
+            # only get_features_detach_rest: the DC part cannot be told from the concatenation it comes in, so the full backward pass
+            # runs and autograd splits its gradient as before -- same result, slower
+            global _warned_no_split
+            if not _warned_no_split:
+                _warned_no_split = True
+                warnings.warn(f"render(appearance_only=True): {type(pc).__name__} offers no split SH tensors (get_features_split_detach_rest, "
+                              "or the reference model's _features_dc / _features_rest with unmodified getters); using the full backward pass")
     if getattr(pc, "row_sparse_grads", False) and raw is not None and isinstance(shs, tuple) and torch.is_grad_enabled():
         extra["row_sparse"] = True
     if cuda_type == "pcheck_obb_loss_weighted_max_count":

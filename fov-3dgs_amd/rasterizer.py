@@ -733,12 +733,14 @@ GRADIENT_RANGES = 4
 def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                      grad_out_color, sh, geomBuffer, num_rendered, binningBuffer, imgBuffer, sh_rest=None,
                      want_cov3D_grad=False, want_color_grad=False, raw_activations=False, row_sparse=False, num_candidates=0, blend_pairs=None,
-                     prezeroed=None):
+                     prezeroed=None, appearance_only=False):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations[, dL_dsh_rest])
     (dL_dsh_rest only with split SH storage: then dL_dsh is the DC part [P,1,3]; dL_dcov3D / dL_dcolors are None unless
     cov3Ds_precomp / colors_precomp are given or want_cov3D_grad / want_color_grad)
     row_sparse (extension, fovraster.h): the tensors are COMPACT, [num_candidates, ...], row i = the gradient of the Gaussian
-    vis_list[i] (visible_rows(): the forward call's list of cull survivors, increasing indices); nothing is zero-filled."""
+    vis_list[i] (visible_rows(): the forward call's list of cull survivors, increasing indices); nothing is zero-filled.
+    appearance_only (extension, fr_backward_appearance): only dL_dopacity, dL_dsh -- ALWAYS the DC part [P,1,3], also for
+    concatenated shs -- and dL_dcolors (as above) are computed and allocated; every other place of the tuple is None."""
     lib = _native.load()
     dev = means3D.device
     P = means3D.size(0)
@@ -770,7 +772,14 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
         # visible Gaussian in its geometry workspace
         has_cov = want_cov3D_grad or (cov3Ds_precomp is not None and cov3Ds_precomp.numel() != 0)
         has_col = want_color_grad or (colors_precomp is not None and colors_precomp.numel() != 0)
-        if prezeroed is not None:
+        if appearance_only:
+            if prezeroed is not None:
+                raise ValueError("appearance_only allocates its own (two or three) gradient tensors: no prezeroed set")
+            dL_dmeans3D = dL_dmeans2D = dL_dcov3D = dL_dscales = dL_drotations = dL_dsh_rest = None
+            dL_dopacity = z(P, 1)
+            dL_dcolors = z(P, 3) if has_col else None
+            dL_dsh = z(P, 1, 3) if M else None
+        elif prezeroed is not None:
             # allocated and zero-filled at the end of the forward call (prefill_gradients), beside the work between the two calls
             (dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dcov3D, dL_dcolors, dL_dsh, dL_dscales, dL_drotations, dL_dsh_rest) = prezeroed
         else:
@@ -797,12 +806,12 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
             put("dL_dpix", grad_out_color)
             a.radii = radii.data_ptr()
             a.geometry, a.binning, a.image = geomBuffer.data_ptr(), _ptr(binningBuffer if binningBuffer.numel() else None), imgBuffer.data_ptr()
-            a.dL_dmean2D, a.dL_dconic, a.dL_dopacity = dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr()
-            a.dL_dcolor, a.dL_dmean3D = (dL_dcolors.data_ptr() if dL_dcolors is not None else None), dL_dmeans3D.data_ptr()
+            a.dL_dmean2D, a.dL_dconic, a.dL_dopacity = _ptr(dL_dmeans2D), None, dL_dopacity.data_ptr()
+            a.dL_dcolor, a.dL_dmean3D = (dL_dcolors.data_ptr() if dL_dcolors is not None else None), _ptr(dL_dmeans3D)
             a.dL_dcov3D = dL_dcov3D.data_ptr() if dL_dcov3D is not None else None
             a.dL_dsh = dL_dsh.data_ptr() if M else None
             a.dL_dsh_rest = dL_dsh_rest.data_ptr() if dL_dsh_rest is not None else None
-            a.dL_dscale, a.dL_drot = dL_dscales.data_ptr(), dL_drotations.data_ptr()
+            a.dL_dscale, a.dL_drot = _ptr(dL_dscales), _ptr(dL_drotations)
             if _bwd_events_hook is not None:
                 a.stage_events = _bwd_events_hook()
             if blend_pairs is not None:
@@ -825,12 +834,14 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
                 keep.append(cb)
                 a.num_ranges = int(GRADIENT_RANGES)
                 a.range_done = C.cast(cb, C.c_void_p)
-            rc = lib.fr_backward(C.byref(a))
+            rc = (lib.fr_backward_appearance if appearance_only else lib.fr_backward)(C.byref(a))
             if rc != 0:
                 raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
             if hook_errors:
                 raise hook_errors[0]
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+    if appearance_only:
+        return out + (None,) if rest_c is not None else out
     return out + (dL_dsh_rest,) if dL_dsh_rest is not None else out
 
 
@@ -878,6 +889,21 @@ def _keep_coalesced_flag(rows, leaves):
     torch.autograd.Variable._execution_engine.queue_callback(restore)
 
 
+def _check_appearance_only(shs=None, **detached):
+    """appearance_only differentiates the opacity and the DC colour (or colors_precomp) and nothing else: an input that asks for any
+    other gradient is an error, never a gradient silently dropped."""
+    if not torch.is_grad_enabled():
+        return
+    for name, t in detached.items():
+        if t is not None and t.requires_grad:
+            what = "the rest SH coefficients (shs[1])" if name == "shs_rest" else name
+            raise ValueError(f"appearance_only: {what} requires grad, but only opacities and the DC colour (or colors_precomp) get a "
+                             "gradient in this mode -- detach it, or call without appearance_only")
+    if shs is not None and shs.requires_grad and shs.dim() == 3 and shs.size(1) > 1:
+        raise ValueError(f"appearance_only: a concatenated shs [P,{shs.size(1)},3] requires grad, but only its DC part gets a gradient "
+                         "in this mode -- pass the split form shs=(features_dc [P,1,3], features_rest.detach())")
+
+
 def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
     """Autograd function + module for the non-foveated variants. takes_loss_map: the
     …_loss_weighted_max_count extension has one extra input (`loss_map`, a [3,H,W] or [H,W] tensor)."""
@@ -886,7 +912,10 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
         @staticmethod
         def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                     raster_settings, loss_map=None, sh_rest=None, packed=None, grad_mode=True, raw_activations=False,
-                    row_sparse=False, want_stats=True):
+                    row_sparse=False, want_stats=True, appearance_only=False):
+            # appearance_only (extension, the mask-learning step: metric_mask_learn.py:213 renders with masking=True and learns the
+            # opacity and the DC colour only): backward is fr_backward_appearance -- gradients for opacities and sh (the DC part) /
+            # colors_precomp, None for everything else (GaussianRasterizer.forward has checked that nothing else wants one)
             # want_stats=False (extension, pcheck_obb_sum): the caller drops gaussians_count / contributions (eff_finetune.py:107-108
             # does): the blend skips them and the call returns (color, radii) only
             # row_sparse (extension): backward returns the gradients of the [P, ...] inputs as SPARSE tensors (torch.sparse_coo, one
@@ -911,6 +940,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             ctx.split_sh = sh_rest is not None
             ctx.raw_activations = bool(raw_activations)
             ctx.row_sparse = bool(row_sparse) and has_backward
+            ctx.appearance_only = bool(appearance_only) and has_backward
             # no zero tensors for the gradients of the outputs nobody differentiates (radii, counts, contributions:
             # three [P] fills per step otherwise)
             ctx.set_materialize_grads(False)
@@ -944,7 +974,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             ctx.num_rendered = num_rendered
             ctx.ws_lease = res[-1] if keep_ws else None
             ctx.prezero = None
-            if keep_ws and PREZERO_GRADIENTS and not ctx.row_sparse and means3D.size(0) > 0:
+            if keep_ws and PREZERO_GRADIENTS and not ctx.row_sparse and not ctx.appearance_only and means3D.size(0) > 0:
                 has_sh = sh.numel() != 0
                 M0 = sh.size(1) if has_sh else 0
                 ctx.prezero = prefill_gradients(means3D.device, means3D.size(0), M0, sh_rest.size(1) if sh_rest is not None else None,
@@ -964,7 +994,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
                 # the reference's inference-only extension exports no backward entry point
                 raise RuntimeError("this rasterizer variant is inference-only (no backward in the reference)")
             if grad_out_color is None:  # the image took no part in the loss
-                return (None,) * 16
+                return (None,) * 17
             rs = ctx.raster_settings
             (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities,
              geomBuffer, binningBuffer, imgBuffer, sh_rest) = ctx.saved_tensors
@@ -972,6 +1002,8 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
                     grad_out_color, sh, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer,
                     sh_rest if ctx.split_sh else None)
             kw = dict(raw_activations=ctx.raw_activations, row_sparse=ctx.row_sparse, num_candidates=ctx.num_candidates)
+            if ctx.appearance_only:
+                kw["appearance_only"] = True
             pre, ctx.prezero = ctx.prezero, None  # (a second backward over the same graph allocates its own tensors)
             if pre is not None:
                 torch.cuda.current_stream(means3D.device).wait_event(pre[1])
@@ -1002,17 +1034,19 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
                 _keep_coalesced_flag(rows, (means3D, sh, opacities, scales, rotations, sh_rest))
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = res[:8]
+            if ctx.appearance_only and not ctx.needs_input_grad[2]:
+                grad_sh = None  # (the DC part [P,1,3]: not the shape of a concatenated sh, which then is no input that wants one)
             grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                      grad_rotations, grad_cov3Ds_precomp, None)
-            # loss_map, sh_rest, packed, grad_mode, raw_activations, row_sparse, want_stats
-            return grads + (None, res[8] if ctx.split_sh else None, None, None, None, None, None)
+            # loss_map, sh_rest, packed, grad_mode, raw_activations, row_sparse, want_stats, appearance_only
+            return grads + (None, res[8] if ctx.split_sh else None, None, None, None, None, None, None)
 
     def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                             raster_settings, loss_map=None, sh_rest=None, packed=None, raw_activations=False, row_sparse=False,
-                            want_stats=True):
+                            want_stats=True, appearance_only=False):
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, raster_settings, loss_map if takes_loss_map else None, sh_rest, packed,
-                                         torch.is_grad_enabled(), raw_activations, row_sparse, want_stats)
+                                         torch.is_grad_enabled(), raw_activations, row_sparse, want_stats, appearance_only)
 
     class GaussianRasterizer(nn.Module):
         def __init__(self, raster_settings):
@@ -1024,7 +1058,8 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
                 return _mark_visible(positions, self.raster_settings)
 
         def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                    cov3D_precomp=None, loss_map=None, packed=None, raw_activations=False, row_sparse=False, want_stats=True):
+                    cov3D_precomp=None, loss_map=None, packed=None, raw_activations=False, row_sparse=False, want_stats=True,
+                    appearance_only=False):
             raster_settings = self.raster_settings
             if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
                 raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -1037,13 +1072,19 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             shs_rest = None
             if isinstance(shs, (tuple, list)):  # extension: (features_dc [P,1,3], features_rest [P,M-1,3])
                 shs, shs_rest = shs
+            if appearance_only:
+                if not has_backward:
+                    raise ValueError("appearance_only: this rasterizer variant has no backward pass")
+                _check_appearance_only(means3D=means3D, means2D=means2D, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
+                                       shs_rest=shs_rest, shs=shs)
             shs = empty if shs is None else shs
             colors_precomp = empty if colors_precomp is None else colors_precomp
             scales = empty if scales is None else scales
             rotations = empty if rotations is None else rotations
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, raster_settings, loss_map, shs_rest, packed, raw_activations, row_sparse, want_stats))
+                                       cov3D_precomp, raster_settings, loss_map, shs_rest, packed, raw_activations, row_sparse, want_stats,
+                                       appearance_only))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 

@@ -300,6 +300,25 @@ int fr_backward(const fr_backward_args *args);
  * would be called; nothing else is read) with one kernel on `fill_stream`; pair with fr_backward_args.outputs_zeroed. No-op for
  * row_sparse. */
 int fr_backward_prefill(const fr_backward_args *args, void *fill_stream);
+/* The backward pass of the mask-learning step (extension; metric_mask_learn.py:213 renders with masking=True, and
+ * gaussian_renderer/__init__.py:71-82 then detaches positions, scales, rotations and the rest SH coefficients): gradients of the
+ * OPACITY and of the DC COLOUR only, over the forward state fr_backward would use, with the same `args` struct. The tile pass sums
+ * four values per (band, entry) pair instead of nine (colour r g b and M00), and a per-Gaussian pass without SH rows or chain rule
+ * writes 16 bytes per visible Gaussian.
+ *   dL_dopacity  [P,1], required; w.r.t. the raw parameter with raw_activations.
+ *   dL_dsh       optional, ALWAYS the DC gradient [P,1,3], whether shs is concatenated [P,M,3] or split (shs_rest given):
+ *                SH_C0 * dL/dcolour, zero for a channel the forward pass clamped (backward.cu:20-139). Needs shs.
+ *   dL_dcolor    optional, [P,3]: dL/dcolour (with colors_precomp: the input's gradient).
+ *   every other dL_d* pointer (dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, dL_dsh_rest) must be NULL:
+ *   FR_ERR_INVALID, the message names the field.
+ * Variants, raw_activations, row_sparse (the outputs are then [C,1] / [C,1,3] / [C,3], every row written), outputs_zeroed,
+ * stage_events ([0] [1] [2] around the two passes, [3] [4] around the zero fill, which runs on `stream` in front of them) and
+ * blend_pairs as for fr_backward; dense outputs are written in full, zero rows included. num_ranges is ignored: the per-Gaussian
+ * pass runs in one piece and range_done, when given, is called exactly once as range_done(range_user, 0, 0, P) behind its launch
+ * (not with row_sparse, not with P == 0). The per-Gaussian sums the call reads are cleared again, so any mix of fr_backward and
+ * fr_backward_appearance calls over one forward state gives each call's gradients as a single call would. Never synchronises.
+ * radii, means3D, scales, rotations, cov3D_precomp, opacities and the matrices are not read. */
+int fr_backward_appearance(const fr_backward_args *args);
 int fr_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, const float *projmatrix,
 	uint8_t *present /* [P] bool */, void *stream);
 
