@@ -57,6 +57,12 @@ class ForwardExt(C.Structure):
     _fields_ = [("size", C.c_uint32), ("visibility", _FP)]
 
 
+class Foveation(C.Structure):
+    """fr_foveation: the layer count and display geometry of one foveated call (fr_forward_begin_fov / fr_forward_fov_call)"""
+    _fields_ = [("size", C.c_uint32), ("levels", C.c_int32), ("max_pooling_size", C.c_float), ("real_image_width", C.c_float),
+                ("real_viewing_distance", C.c_float), ("start_blend", C.c_float), ("blend_width", C.c_float)]
+
+
 class BackwardArgs(C.Structure):
     _fields_ = [
         ("variant", C.c_int32), ("P", C.c_int32), ("D", C.c_int32), ("M", C.c_int32), ("R", C.c_int32),
@@ -146,10 +152,14 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_adam_step",
            "fr_prune_workspace_bytes", "fr_prune_metric_max", "fr_prune_select_lowest", "fr_compact_plan", "fr_compact_rows",
            "fr_densify_workspace_bytes", "fr_densify_stats", "fr_densify_plan", "fr_densify_rows",
-           "fr_forward_begin_ext", "fr_forward_ext_call", "fr_backward_appearance")
+           "fr_forward_begin_ext", "fr_forward_ext_call", "fr_backward_appearance",
+           "fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
-OPTIONAL_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
+EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
+# ... and the foveation settings (fr_foveation): has_foveation(); without them only the reference's constants render
+FOVEATION_EXPORTS = ("fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov")
+OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS
 
 _lib = None
 
@@ -236,6 +246,17 @@ def load():
         lib.fr_forward_begin_ext.restype = C.c_int
         lib.fr_forward_ext_call.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt)]
         lib.fr_forward_ext_call.restype = C.c_int
+    if has_foveation(lib):
+        lib.fr_forward_begin_fov.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(C.c_void_p)]
+        lib.fr_forward_begin_fov.restype = C.c_int
+        lib.fr_forward_fov_call.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation)]
+        lib.fr_forward_fov_call.restype = C.c_int
+        lib.fr_geometry_bytes_fov.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        lib.fr_geometry_bytes_fov.restype = C.c_size_t
+        lib.fr_geometry_level_colours_hi.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        lib.fr_geometry_level_colours_hi.restype = C.c_void_p
+        lib.fr_pack_colour_fov.argtypes = [C.c_int32, _FP, _FP, C.c_int32, _FP, C.c_void_p]
+        lib.fr_pack_colour_fov.restype = C.c_int
     lib.fr_forward_finish.argtypes = [C.c_void_p]
     lib.fr_forward_finish.restype = C.c_int
     lib.fr_backward_prefill.argtypes = [C.POINTER(BackwardArgs), C.c_void_p]
@@ -275,7 +296,13 @@ def load():
 def has_forward_ext(lib=None):
     """the loaded library writes fr_forward_ext.visibility (else: compute it from radii)"""
     lib = load() if lib is None else lib
-    return all(hasattr(lib, n) for n in OPTIONAL_EXPORTS)
+    return all(hasattr(lib, n) for n in EXT_EXPORTS)
+
+
+def has_foveation(lib=None):
+    """the loaded library takes fr_foveation settings (else: only the reference's constants, and anything else is refused)"""
+    lib = load() if lib is None else lib
+    return all(hasattr(lib, n) for n in FOVEATION_EXPORTS)
 
 
 def last_error():

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <cmath>
 #include <new>
 
 namespace fr {
@@ -84,6 +85,42 @@ static int validate_forward(const fr_forward_args *a)
 	return FR_OK;
 }
 
+// fr_foveation -> what the kernels take. The level step and the cap are formed HERE, once, in the reference's order of operations
+// (RF rasterizer_impl.cu:99-177 with the constants of auxiliary.h:26-32 replaced), so that every kernel and a CPU derivation
+// that does the same arithmetic use the same floats. f == NULL: the reference's constants.
+static FovParams fov_params(const fr_foveation *f)
+{
+	FovParams p;
+	p.levels = f ? f->levels : FR_FOV_LEVELS;
+	const float sqrt_max_ps = (float)sqrt((double)(f ? f->max_pooling_size : 12.0f)); // 12: the reference's literal 3.4641016151377544f
+	p.riw = f ? f->real_image_width : 2.0f;
+	p.rvd = f ? f->real_viewing_distance : 1.0f;
+	p.step = (float)(((double)sqrt_max_ps - 1.) / (double)(float)(p.levels - 1));
+	p.cap = (float)((double)(float)p.levels - 0.1);
+	p.start_blend = f ? f->start_blend : 0.5f;
+	p.blend_width = f ? f->blend_width : 0.5f;
+	p.box_top = (float)(p.levels > FR_FOV_LEVELS ? p.levels : FR_FOV_LEVELS);
+	return p;
+}
+
+// refuses a bad fr_foveation before anything is enqueued; the message names the field
+static int validate_foveation(const fr_forward_args *a, const fr_foveation *f)
+{
+	if (!f) return FR_OK;
+	if (f->size < sizeof(fr_foveation)) { set_error("fr_foveation.size is %u, expected at least %u", f->size, (unsigned)sizeof(fr_foveation)); return FR_ERR_INVALID; }
+	if (a->variant != FR_VARIANT_FOV_PCHECK_OBB)
+	{ set_error("fr_foveation: settings are for variant %d (fov_pcheck_obb) only, not variant %d (the SMFR / MMFR baselines keep the reference's constants)", FR_VARIANT_FOV_PCHECK_OBB, a->variant); return FR_ERR_INVALID; }
+	if (f->levels < 2 || f->levels > FR_FOV_MAX_LEVELS) { set_error("fr_foveation.levels is %d, not in 2..%d", f->levels, FR_FOV_MAX_LEVELS); return FR_ERR_INVALID; }
+	if (!std::isfinite(f->max_pooling_size) || !(f->max_pooling_size > 1.0f)) { set_error("fr_foveation.max_pooling_size is %g, must be finite and > 1", (double)f->max_pooling_size); return FR_ERR_INVALID; }
+	if (!std::isfinite(f->real_image_width) || !(f->real_image_width > 0.0f)) { set_error("fr_foveation.real_image_width is %g, must be finite and > 0", (double)f->real_image_width); return FR_ERR_INVALID; }
+	if (!std::isfinite(f->real_viewing_distance) || !(f->real_viewing_distance > 0.0f)) { set_error("fr_foveation.real_viewing_distance is %g, must be finite and > 0", (double)f->real_viewing_distance); return FR_ERR_INVALID; }
+	if (!std::isfinite(f->start_blend) || !(f->start_blend > 0.0f && f->start_blend < 1.0f)) { set_error("fr_foveation.start_blend is %g, must lie in (0, 1)", (double)f->start_blend); return FR_ERR_INVALID; }
+	if (!std::isfinite(f->blend_width) || !(f->blend_width > 0.0f)) { set_error("fr_foveation.blend_width is %g, must be finite and > 0", (double)f->blend_width); return FR_ERR_INVALID; }
+	if (f->levels > FR_FOV_LEVELS && (a->packed_geom || a->packed_colour || a->packed_cull))
+	{ set_error("fr_foveation.levels is %d: the packed model layout holds at most %d levels", f->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
 } // namespace fr
 
 using namespace fr;
@@ -112,6 +149,11 @@ int fr_event_elapsed_ms(void *start, void *stop, float *ms)
 const char *fr_last_error(void) { return g_err; }
 
 size_t fr_geometry_bytes(int32_t variant, int32_t P) { return carve_geom(variant, (size_t)P, nullptr).bytes; }
+size_t fr_geometry_bytes_fov(int32_t variant, int32_t P, int32_t levels)
+{
+	if (P < 0 || levels < 2 || levels > FR_FOV_MAX_LEVELS) { set_error("bad geometry_bytes_fov arguments"); return 0; }
+	return carve_geom(variant, (size_t)P, nullptr, levels).bytes;
+}
 size_t fr_image_bytes(int32_t variant, int32_t W, int32_t H) { return carve_image(variant, W, H, nullptr).bytes; }
 size_t fr_binning_bytes(int32_t variant, int64_t n) { (void)variant; return carve_bin(n, nullptr).bytes; }
 
@@ -124,6 +166,7 @@ const uint32_t *fr_geometry_vis_list(int32_t variant, int32_t P, const char *geo
 const uint32_t *fr_geometry_vis_count(int32_t variant, int32_t P, const char *geometry) { return carve_geom(variant, (size_t)P, (char *)geometry).slab_ctr + 1; }
 const float *fr_geometry_walk_records(int32_t variant, int32_t P, const char *geometry) { return (const float *)carve_geom(variant, (size_t)P, (char *)geometry).wrec; }
 const float *fr_geometry_level_colours(int32_t P, const char *geometry) { return (const float *)carve_geom(FR_VARIANT_FOV_PCHECK_OBB, (size_t)P, (char *)geometry).lvl; }
+const float *fr_geometry_level_colours_hi(int32_t P, int32_t levels, const char *geometry) { return (const float *)carve_geom(FR_VARIANT_FOV_PCHECK_OBB, (size_t)P, (char *)geometry, levels).lvl_hi; }
 const uint32_t *fr_geometry_level_ranges(int32_t P, const char *geometry) { return carve_geom(FR_VARIANT_FOV_PCHECK_OBB, (size_t)P, (char *)geometry).lrange; }
 const float *fr_image_tile_levels(int32_t W, int32_t H, const char *image) { return carve_image(FR_VARIANT_FOV_PCHECK_OBB, W, H, (char *)image).tile_lv; }
 
@@ -220,13 +263,15 @@ struct fr_frame
 
 extern "C" {
 
-int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame **out)
+int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **out)
 {
 	if (!out) { set_error("null frame handle"); return FR_ERR_INVALID; }
 	*out = nullptr;
 	int rc = validate_forward(a);
 	if (rc) return rc;
 	if (ext && ext->size < sizeof(fr_forward_ext)) { set_error("fr_forward_ext.size is %u, expected at least %u", ext->size, (unsigned)sizeof(fr_forward_ext)); return FR_ERR_INVALID; }
+	rc = validate_foveation(a, fov);
+	if (rc) return rc;
 	hipStream_t stream = (hipStream_t)a->stream;
 	a->num_rendered = 0;
 	a->max_tile_instances = 0;
@@ -238,6 +283,7 @@ int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame
 	FwdCtx &c = f->c;
 	c.a = a; c.stream = stream;
 	c.visibility = ext ? ext->visibility : nullptr; // (read here: ext need not outlive this call)
+	c.fov = fov_params(fov);                        // (likewise: the settings travel in the kernels' arguments)
 	if (a->P == 0)
 	{
 		// reference: RasterizeGaussiansCUDA returns the zero-initialised image when P == 0
@@ -252,10 +298,10 @@ int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame
 	c.focal_y = a->H / (2.0f * a->tanfovy);
 	c.focal_x = a->W / (2.0f * a->tanfovx);
 
-	char *gptr = a->geometry_resize(a->resize_user[0], carve_geom(a->variant, (size_t)a->P, nullptr).bytes);
+	char *gptr = a->geometry_resize(a->resize_user[0], carve_geom(a->variant, (size_t)a->P, nullptr, c.fov.levels).bytes);
 	char *iptr = a->image_resize(a->resize_user[2], carve_image(a->variant, a->W, a->H, nullptr).bytes);
 	if (!gptr || !iptr) { set_error("geometry/image resize callback returned null"); return FR_ERR_ALLOC; }
-	c.geom = carve_geom(a->variant, (size_t)a->P, gptr);
+	c.geom = carve_geom(a->variant, (size_t)a->P, gptr, c.fov.levels);
 	c.img = carve_image(a->variant, a->W, a->H, iptr);
 
 	// RF: the two level states of a two-level tile are blended by different waves, which ADD their halves to the image: those
@@ -298,6 +344,7 @@ int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame
 	c.totals_seq = seq;
 	mark(FR_STAGE_TILE_LEVELS);
 	if (is_fov(a->variant)) { rc = launch_tile_levels(c); if (rc) return rc; }
+	if (c.geom.pad_op) { rc = launch_pad_levels(c); if (rc) return rc; } // (fr_foveation.levels other than 4 and 8)
 	mark(FR_STAGE_PROJECT);
 	rc = launch_project(c); if (rc) return rc;
 	int cur_dev = 0;
@@ -406,15 +453,18 @@ int fr_forward_abandon(fr_frame *f)
 	return FR_OK;
 }
 
-int fr_forward_begin(fr_forward_args *a, fr_frame **out) { return fr_forward_begin_ext(a, nullptr, out); }
+int fr_forward_begin_ext(fr_forward_args *a, const fr_forward_ext *ext, fr_frame **out) { return fr_forward_begin_fov(a, ext, nullptr, out); }
+int fr_forward_begin(fr_forward_args *a, fr_frame **out) { return fr_forward_begin_fov(a, nullptr, nullptr, out); }
 
-int fr_forward_ext_call(fr_forward_args *a, const fr_forward_ext *ext)
+int fr_forward_fov_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov)
 {
 	fr_frame *f = nullptr;
-	const int rc = fr_forward_begin_ext(a, ext, &f);
+	const int rc = fr_forward_begin_fov(a, ext, fov, &f);
 	if (rc) return rc;
 	return fr_forward_finish(f);
 }
+
+int fr_forward_ext_call(fr_forward_args *a, const fr_forward_ext *ext) { return fr_forward_fov_call(a, ext, nullptr); }
 
 int fr_forward(fr_forward_args *a) { return fr_forward_ext_call(a, nullptr); }
 
@@ -439,6 +489,13 @@ int fr_pack_colour(int32_t P, const float *shs, const float *shs_rest, const flo
 	if (P < 0 || (P > 0 && (!shs || !packed_colour)) || (shs_rest && shs_dcs)) { set_error("bad pack_colour arguments"); return FR_ERR_INVALID; }
 	if (P == 0) return FR_OK;
 	return launch_pack_colour(P, shs, shs_rest, shs_dcs, packed_colour, (hipStream_t)stream);
+}
+
+int fr_pack_colour_fov(int32_t P, const float *shs, const float *shs_dcs, int32_t levels, float *packed_colour, void *stream)
+{
+	if (P < 0 || levels < 1 || levels > FR_FOV_LEVELS || (P > 0 && (!shs || !shs_dcs || !packed_colour))) { set_error("bad pack_colour_fov arguments"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_pack_colour(P, shs, nullptr, shs_dcs, packed_colour, (hipStream_t)stream, levels);
 }
 
 int fr_activate_forward(int32_t P, const float *raw_scaling, const float *raw_rotation, const float *raw_opacity, float *scaling, float *rotation,

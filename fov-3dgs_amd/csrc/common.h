@@ -7,7 +7,8 @@
 
 #define FR_TILE 16            // tile edge in pixels (reference config.h:15-17 BLOCK_X/BLOCK_Y)
 #define FR_TILE_PIX 256
-#define FR_FOV_LEVELS 4       // RF auxiliary.h:26 fov_num
+#define FR_FOV_LEVELS 4       // RF auxiliary.h:26 fov_num: the layer count of a call without fr_foveation, and the level rows of one k_bin instantiation
+#define FR_FOV_MAX_LEVELS 8   // fr_foveation.levels at most: level_ranges keeps a level in 8 bits, the second k_bin instantiation eight rows
 #define FR_SORT_LDS_MAX 8192  // longest per-tile list sorted inside LDS (64 KiB of u64 keys)
 #ifndef FR_BIN_THREADS
 #define FR_BIN_THREADS 768    // workgroup size of k_bin and k_emit (one persistent workgroup per CU): twelve waves hide each other's round trips
@@ -40,10 +41,25 @@ namespace fr {
 
 // variant traits
 #define FR_VARIANT_SUM_NOSTATS 100 // internal (k_render only): pcheck_obb_sum's blend without gaussians_count / contributions
+#define FR_VARIANT_FOV8 101        // internal (k_bin only): FOV_PCHECK_OBB with fr_foveation.levels 5 .. 8 -- eight level rows per item
 __host__ __device__ inline bool has_stats(int v) { return v == FR_VARIANT_PCHECK_OBB_SUM || v == FR_VARIANT_PCHECK_OBB_MAX || v == FR_VARIANT_PCHECK_OBB_LWMC; }
 __host__ __device__ inline bool has_backward(int v) { return v == FR_VARIANT_ORIGINAL || has_stats(v); }
 // variants that bin by eccentricity level (tile level map, level filter): RF and the shared-model baseline
-__host__ __device__ constexpr inline bool is_fov(int v) { return v == FR_VARIANT_FOV_PCHECK_OBB || v == FR_VARIANT_NAIVE_FOV_PCHECK_OBB || v == FR_VARIANT_MMFR_PCHECK_OBB; }
+__host__ __device__ constexpr inline bool is_fov(int v) { return v == FR_VARIANT_FOV_PCHECK_OBB || v == FR_VARIANT_FOV8 || v == FR_VARIANT_NAIVE_FOV_PCHECK_OBB || v == FR_VARIANT_MMFR_PCHECK_OBB; }
+// per-level colours / opacities (RF), and the level rows an instantiation keeps per item
+__host__ __device__ constexpr inline bool is_levelcol(int v) { return v == FR_VARIANT_FOV_PCHECK_OBB || v == FR_VARIANT_FOV8; }
+__host__ __device__ constexpr inline int level_rows(int v) { return v == FR_VARIANT_FOV8 ? FR_FOV_MAX_LEVELS : FR_FOV_LEVELS; }
+
+// fr_foveation as the kernels take it: wave-uniform arguments (scalar registers), formed once on the host (api.hip fov_params) so
+// that every kernel -- and a CPU derivation that does the same arithmetic -- uses the same floats
+struct FovParams {
+	int levels;         // L
+	float riw, rvd;     // real_image_width, real_viewing_distance
+	float step;         // float((double(sqrt_max_ps) - 1.) / double(float(L - 1))): pooling-size root per level (RF rasterizer_impl.cu:99-177)
+	float cap;          // float(double(float(L)) - 0.1): the highest level a tile takes
+	float start_blend, blend_width;
+	float box_top;      // float(max(L, 4)): the bound of level box 4 (k_tile_levels)
+};
 
 // ---- workspace layouts -------------------------------------------------------------------
 // All sub-arrays are 256-byte aligned inside the caller's buffers.
@@ -71,7 +87,7 @@ struct GeomWS {
 	float4 *wrec;       // [4P] walk record of item i at [4i..4i+3], written by k_bin for k_emit:
 	                    //      (cx, cy, e1x, e1y | e2x, e2y, len1, len2 | Gaussian index + flags << 30, depth bits, x0 + y0 << 16, width |
 	                    //      tiles, highest level, -, -); flags: 1 = lands in a tile, 2 = the OBB test applies
-	float4 *lvl;        // [4P] RF per-level (r,g,b,opacity) of item i at [4i..4i+3] (k_bin)
+	float4 *lvl;        // [4P] RF per-level (r,g,b,opacity) of item i at [4i..4i+3] (k_bin): the levels 0 .. 3 (4 .. 7: lvl_hi)
 	uint32_t *lrange;   // [P]  per item, written by k_bin: 0xffffffff = the item lands in no tile (culled everywhere), else the packed
 	                    //      level range lo | hi<<8 (RF; 0 for the variants without levels)
 	uint32_t *slab_ctr; // [FR_SLAB_CTR_WORDS] {prefiltered violation flag, number of entries in vis_list, workgroups of the cull pass that
@@ -85,9 +101,14 @@ struct GeomWS {
 	                       // every wave's region; [waves] = the number of items
 	float4 *crow;       // [3 (P + FR_CROW_PAD)] foveated variants' candidate rows (xyz, scale | scale.yz, rotation.xy | rotation.zw, highest
 	                    //      level, index), same slots as vis_seg ...
+	// fr_foveation.levels other than 4 (behind everything above: no other array moves)
+	float4 *lvl_hi;     // levels > 4: [4P] the rows of the levels 4 .. 7, as lvl keeps those of 0 .. 3
+	float *pad_op;      // levels not 4 or 8: [P][Lp] the caller's opacities [P,L] in rows of Lp = 4 (L < 4) or 8 floats, the rest zero ...
+	float *pad_dc;      // ... and [P][Lp][3] its shs_dcs [P,L,3] (k_pad_levels): colour_item fetches whole 16-byte pieces
 	size_t bytes;
 };
-__host__ __device__ inline GeomWS carve_geom(int variant, size_t P, char *base)
+__host__ __device__ inline int padded_levels(int levels) { return levels <= FR_FOV_LEVELS ? FR_FOV_LEVELS : FR_FOV_MAX_LEVELS; }
+__host__ __device__ inline GeomWS carve_geom(int variant, size_t P, char *base, int levels = FR_FOV_LEVELS)
 {
 	GeomWS g; size_t off = 0;
 	g.rec = (float4 *)(base + off); off = align_up(off + P * 3 * sizeof(float4));
@@ -110,6 +131,13 @@ __host__ __device__ inline GeomWS carve_geom(int variant, size_t P, char *base)
 	// training frames need not carry
 	g.crow = nullptr;
 	if (is_fov(variant)) { g.crow = (float4 *)(base + off); off = align_up(off + (P + FR_CROW_PAD) * 3 * sizeof(float4)); }
+	g.lvl_hi = nullptr; g.pad_op = nullptr; g.pad_dc = nullptr;
+	if (variant == FR_VARIANT_FOV_PCHECK_OBB && levels > FR_FOV_LEVELS) { g.lvl_hi = (float4 *)(base + off); off = align_up(off + P * FR_FOV_LEVELS * sizeof(float4)); }
+	if (variant == FR_VARIANT_FOV_PCHECK_OBB && levels != padded_levels(levels))
+	{
+		g.pad_op = (float *)(base + off); off = align_up(off + P * padded_levels(levels) * sizeof(float));
+		g.pad_dc = (float *)(base + off); off = align_up(off + P * padded_levels(levels) * 3 * sizeof(float));
+	}
 	g.bytes = off + 256;
 	return g;
 }
@@ -247,6 +275,8 @@ __device__ __forceinline__ WalkRect walk_rect(float px, float py, int radius, in
 	}
 	if (FOV)
 	{
+		// (box 4 holds the tiles with tile_min < max(L, 4), i.e. every tile with a level: with fr_foveation.levels > 4 the highest
+		// levels 3 .. L-1 share it -- the clip is conservative, the level test proper follows per tile)
 		const int k = (int)fminf(fmaxf(ceilf(hl + 1.0f), 0.0f), 4.0f); // NaN -> 0: nothing passes `level < NaN`
 		const uint4 b = lv_boxes[k * lv_box_stride];
 		w.x0 = max(w.x0, gx - (int)b.x); w.y0 = max(w.y0, gy - (int)b.y);
@@ -434,6 +464,7 @@ struct FwdCtx {
 	uint32_t *totals_host_dev; // device address of the host's pinned copy of totals[4] (+ sequence word), or null
 	uint32_t totals_seq;       // this frame's sequence number for that word
 	float focal_x, focal_y;
+	FovParams fov;      // foveated variants: the call's fr_foveation (the reference's constants without one)
 	GeomWS geom;
 	ImageWS img;
 	BinWS bin;
@@ -441,10 +472,11 @@ struct FwdCtx {
 struct AuxStream { int device = -1; hipStream_t main = nullptr, s, s2; hipEvent_t fork, fork2, join, join2; bool ok = false; };
 AuxStream *aux_stream(hipStream_t main); // helper streams of the calling host thread for work launched on `main` (binning.hip)
 int launch_tile_levels(FwdCtx &c);
+int launch_pad_levels(FwdCtx &c); // fr_foveation.levels other than 4 and 8: GeomWS::pad_op / pad_dc
 int launch_pack_geom(int P, const float *means3D, const float *scales, const float *rotations, const float *opacities, int levels,
 	const float *highest_levels, float *out, hipStream_t stream);
 int launch_pack_cull(int P, const float *means3D, const float *scales, const float *rotations, float *out, hipStream_t stream);
-int launch_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out, hipStream_t stream);
+int launch_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out, hipStream_t stream, int levels = FR_FOV_LEVELS);
 int launch_l1_ssim_forward(int C, int H, int W, const float *x, const float *y, float *dmaps, float *partials, hipStream_t stream);
 int launch_l1_ssim_finish(int nblocks, double n, const float *partials, float lam, float *out3, hipStream_t stream);
 int launch_l1_ssim_backward(int C, int H, int W, const float *x, const float *y, const float *dmaps, float w_l1, float w_ssim,

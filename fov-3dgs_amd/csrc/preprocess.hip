@@ -49,23 +49,24 @@ __device__ __forceinline__ M3 m3_t(const M3 &a)
 }
 
 // ---- RF eccentricity level of a tile: RF rasterizer_impl.cu:86-177, auxiliary.h:55-66 ----------
-__device__ __forceinline__ void ncd2dir(float nx, float ny, float rw, float rh, float out[3])
+// (rvd: the viewing distance, RF rasterizer_impl.cu:104 -- the reference's constant is 1)
+__device__ __forceinline__ void ncd2dir(float nx, float ny, float rw, float rh, float rvd, float out[3])
 {
-	const float vx = (nx - 0.5f) * rw, vy = (ny - 0.5f) * rh, vz = 1.0f;
+	const float vx = (nx - 0.5f) * rw, vy = (ny - 0.5f) * rh, vz = rvd;
 	const float d = sqrtf(vx * vx + vy * vy + vz * vz);
 	out[0] = vx / d; out[1] = vy / d; out[2] = vz / d;
 }
-__device__ float tile_level(int tx, int ty, int W, int H, float gaze_x, float gaze_y, float alpha)
+// fp: the call's fr_foveation (wave-uniform; the reference compiles riw = 2, rvd = 1, sqrt_max_ps = sqrt(12), four levels in)
+__device__ float tile_level(int tx, int ty, int W, int H, float gaze_x, float gaze_y, float alpha, const FovParams fp)
 {
-	const float riw = 2.0f, rvd = 1.0f, sqrt_max_ps = 3.4641016151377544f;
-	const float step = (float)(((double)sqrt_max_ps - 1.) / (double)(float)(FR_FOV_LEVELS - 1));
+	const float riw = fp.riw, rvd = fp.rvd, step = fp.step;
 	const float px = (float)(tx * FR_TILE + FR_TILE / 2), py = (float)(ty * FR_TILE + FR_TILE / 2);
 	const float rih = (float)H / (float)W * riw;
 	const float nx = px / W, ny = py / H;
 	float tdir[3], gdir[3], cdir[3];
-	ncd2dir(nx, ny, riw, rih, tdir);
-	ncd2dir(gaze_x, gaze_y, riw, rih, gdir);
-	ncd2dir(0.5f, 0.5f, riw, rih, cdir);
+	ncd2dir(nx, ny, riw, rih, rvd, tdir);
+	ncd2dir(gaze_x, gaze_y, riw, rih, rvd, gdir);
+	ncd2dir(0.5f, 0.5f, riw, rih, rvd, cdir);
 	const float ecc = acosf(gdir[0] * tdir[0] + gdir[1] * tdir[1] + gdir[2] * tdir[2]);
 	const float ecc_c = acosf(tdir[0] * cdir[0] + tdir[1] * cdir[1] + tdir[2] * cdir[2]);
 	const float pool = alpha * ecc * ecc;
@@ -80,7 +81,9 @@ __device__ float tile_level(int tx, int ty, int W, int H, float gaze_x, float ga
 	const float ps = sqrtf(area) * r2p;
 	float level;
 	if (ps <= 1) level = 0; else level = (sqrtf(ps) - 1) / step;
-	if ((double)level > ((double)(float)FR_FOV_LEVELS - 0.1)) level = (float)((double)(float)FR_FOV_LEVELS - 0.1);
+	// the reference: if ((double)level > (double)(float)L - 0.1) level = (float)((double)(float)L - 0.1) -- the same floats either
+	// way the bound rounds: a float above the double bound is at least its float, and the float itself maps to itself
+	if (level > fp.cap) level = fp.cap;
 	return level;
 }
 
@@ -95,7 +98,7 @@ __device__ float tile_level(int tx, int ty, int W, int H, float gaze_x, float ga
 // skipped ones -- with highest_levels == 0 the filter `row 1 < highest_level + 1` is then exactly "not skipped".
 #define FR_LV_PATCH 14 // tiles per side a workgroup of k_tile_levels owns (+ a one-tile halo = its 16 x 16 threads)
 __global__ void __launch_bounds__(256) k_tile_levels(int T, int gx, int gy, int W, int H, float gaze_x, float gaze_y, float alpha, float *out,
-	uint32_t *lv_bbox, uint32_t *slab_ctr, float mmfr_level)
+	uint32_t *lv_bbox, uint32_t *slab_ctr, float mmfr_level, const FovParams fp)
 {
 	// the counters of the two kernels that follow are cleared here (one fill command less at the head of the frame)
 	if (blockIdx.x == 0)
@@ -111,7 +114,7 @@ __global__ void __launch_bounds__(256) k_tile_levels(int T, int gx, int gy, int 
 	const bool in_grid = tx >= 0 && tx < gx && ty >= 0 && ty < gy;
 	const bool live = in_grid && lx >= 1 && lx <= FR_LV_PATCH && ly >= 1 && ly <= FR_LV_PATCH; // a tile this workgroup owns
 	const int idx = ty * gx + tx;
-	s_lv[ly][lx] = in_grid ? tile_level(tx, ty, W, H, gaze_x, gaze_y, alpha) : -1.0f;
+	s_lv[ly][lx] = in_grid ? tile_level(tx, ty, W, H, gaze_x, gaze_y, alpha, fp) : -1.0f;
 	__syncthreads();
 	const float lf = s_lv[ly][lx];
 	const int xl = max(lx - 1, 0), xr = min(lx + 1, 15), yd = max(ly - 1, 0), yu = min(ly + 1, 15); // (only owned tiles use them)
@@ -128,7 +131,7 @@ __global__ void __launch_bounds__(256) k_tile_levels(int T, int gx, int gy, int 
 	float tmin = lf - max_delta;
 	if (mmfr && tmin < 0.0f) tmin = 0.0f;
 	const float tmin_i = (float)f2i(tmin);
-	const bool blending = ((tmin - tmin_i) > 0.5f) && (tmin_i < (float)(FR_FOV_LEVELS - 1));
+	const bool blending = ((tmin - tmin_i) > fp.start_blend) && (tmin_i < (float)(fp.levels - 1));
 	const float real_tmin = tmin;
 	if (mmfr) tmin = (real_tmin > mmfr_level - 0.5f && real_tmin < mmfr_level + 1.0f) ? 0.0f : 5.0f; // the filter key
 	if (live)
@@ -146,7 +149,8 @@ __global__ void __launch_bounds__(256) k_tile_levels(int T, int gx, int gy, int 
 	__syncthreads();
 	for (int k = 0; k <= FR_FOV_LEVELS; k++)
 	{
-		const bool in = live && tmin < (float)k;
+		// (the last box takes every tile with a level: tile_min < max(L, 4), see walk_rect)
+		const bool in = live && tmin < (k == FR_FOV_LEVELS ? fp.box_top : (float)k);
 		uint32_t v[4] = { in ? (uint32_t)(gx - tx) : 0u, in ? (uint32_t)(gy - ty) : 0u, in ? (uint32_t)(tx + 1) : 0u, in ? (uint32_t)(ty + 1) : 0u };
 #pragma unroll
 		for (int c = 0; c < 4; c++)
@@ -284,6 +288,7 @@ struct PreArgs {
 	const float *tile_lv; // RF float[5][T]
 	const uint32_t *lv_bbox; // RF [5][FR_LV_BBOX_STRIDE], see walk_rect()
 	int lds_tiles;           // RF: tile_min and the blend flags are staged in LDS (see k_bin)
+	int levels;              // RF: fr_foveation.levels (a blending Gaussian's level range ends at min(hi + 1, levels - 1))
 	int T;
 	int *radii;
 	uint8_t *visibility;  // [P] 0/1 = radii > 0, written wherever radii is (fr_forward_ext), or null
@@ -883,7 +888,7 @@ __device__ __forceinline__ void geom_item(const PreArgs &a, const float *cam_vm,
 {
 	constexpr bool CULL = VARIANT != FR_VARIANT_ORIGINAL;
 	constexpr bool FOV = is_fov(VARIANT);
-	constexpr bool LEVELCOL = VARIANT == FR_VARIANT_FOV_PCHECK_OBB;
+	constexpr bool LEVELCOL = is_levelcol(VARIANT);
 	Proj pr; pr.alive = false; pr.tnum = 0; pr.x0 = pr.y0 = pr.x1 = pr.y1 = 0; pr.radius = 0;
 	pr.pix_x = pr.pix_y = pr.depth = pr.conic_a = pr.conic_b = pr.conic_c = 0.f;
 #pragma unroll
@@ -939,10 +944,10 @@ __device__ __forceinline__ void geom_item(const PreArgs &a, const float *cam_vm,
 // colour slots); on return the record with opacity / colour / clamp bits (variants with one colour per Gaussian) or, RF, the
 // level rows lv[lo..hi] of the item's level range lr (the others stay zero: nobody reads them).
 template <int VARIANT, bool PACKED>
-__device__ __forceinline__ void colour_item(const PreArgs &a, const bool rows_ok, const uint32_t lr, float4 (&r)[3], float4 (&lv)[FR_FOV_LEVELS])
+__device__ __forceinline__ void colour_item(const PreArgs &a, const bool rows_ok, const uint32_t lr, float4 (&r)[3], float4 (&lv)[level_rows(VARIANT)])
 {
 	constexpr bool FOV = is_fov(VARIANT);
-	constexpr bool LEVELCOL = VARIANT == FR_VARIANT_FOV_PCHECK_OBB;
+	constexpr bool LEVELCOL = is_levelcol(VARIANT);
 	const int idx = __float_as_int(r[2].w);
 	const float dirx = r[1].z - a.campos[0], diry = r[1].w - a.campos[1], dirz = r[2].x - a.campos[2];
 	const float *pcol = PACKED ? a.packed_colour + 64 * (size_t)idx : nullptr;
@@ -988,9 +993,13 @@ __device__ __forceinline__ void colour_item(const PreArgs &a, const bool rows_ok
 	{
 		// RF rasterizer_impl.cu:490-530: per-level colours; all four levels' DC colours (12 floats) and opacities are fetched
 		// with the SH coefficients: one round trip
-		const f4u *dcp = (const f4u *)(PACKED ? pcol + 48 : a.shs_dcs + (size_t)idx * 3 * FR_FOV_LEVELS);
+		// (NLV = 8, fr_foveation.levels > 4: rows of eight levels -- the caller's, or the library's padded copies -- and the block
+		// below a second time over the levels 4 .. 7; the rest-SH colour is evaluated once)
+		constexpr int NLV = level_rows(VARIANT);
+		static_assert(!(PACKED && NLV != FR_FOV_LEVELS), "the packed layout holds four levels");
+		const f4u *dcp = (const f4u *)(PACKED ? pcol + 48 : a.shs_dcs + (size_t)idx * 3 * NLV);
 		const f4u dc0 = dcp[0], dc1 = dcp[1], dc2 = dcp[2];
-		const f4u opl = *(const f4u *)(PACKED ? a.packed_geom + 16 * (size_t)idx + 12 : a.opacities + (size_t)idx * FR_FOV_LEVELS);
+		const f4u opl = *(const f4u *)(PACKED ? a.packed_geom + 16 * (size_t)idx + 12 : a.opacities + (size_t)idx * NLV);
 		float rest[3];
 		if (rows_ok)
 		{
@@ -1014,6 +1023,27 @@ __device__ __forceinline__ void colour_item(const PreArgs &a, const bool rows_ok
 				v.z = fmaxf(FR_SH_C0 * dcs[3 * l + 2] + rest[2], 0.0f);
 				v.w = ops[l];
 				lv[l] = v;
+			}
+		}
+		if (NLV > FR_FOV_LEVELS && hi >= FR_FOV_LEVELS)
+		{
+			const f4u dh0 = dcp[3], dh1 = dcp[4], dh2 = dcp[5];
+			const f4u oph = *(const f4u *)(a.opacities + (size_t)idx * NLV + FR_FOV_LEVELS);
+			const float dch[12] = { dh0.x, dh0.y, dh0.z, dh0.w, dh1.x, dh1.y, dh1.z, dh1.w, dh2.x, dh2.y, dh2.z, dh2.w };
+			const float oh[4] = { oph.x, oph.y, oph.z, oph.w };
+#pragma unroll
+			for (int l = FR_FOV_LEVELS; l < NLV; l++)
+			{
+				if (l >= lo && l <= hi)
+				{
+					const int m = l - FR_FOV_LEVELS;
+					float4 v;
+					v.x = fmaxf(FR_SH_C0 * dch[3 * m] + rest[0], 0.0f);
+					v.y = fmaxf(FR_SH_C0 * dch[3 * m + 1] + rest[1], 0.0f);
+					v.z = fmaxf(FR_SH_C0 * dch[3 * m + 2] + rest[2], 0.0f);
+					v.w = oh[m];
+					lv[l] = v;
+				}
 			}
 		}
 	}
@@ -1051,7 +1081,9 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	static_assert(!(PACKED && CROW), "the packed model layout has its own rows");
 	constexpr bool CULL = VARIANT != FR_VARIANT_ORIGINAL;
 	constexpr bool FOV = is_fov(VARIANT);                            // level map + level filter
-	constexpr bool LEVELCOL = VARIANT == FR_VARIANT_FOV_PCHECK_OBB;  // per-level colours / opacities (RF)
+	constexpr bool LEVELCOL = is_levelcol(VARIANT);                  // per-level colours / opacities (RF)
+	constexpr int NLV = level_rows(VARIANT);                         // level rows per item: 4, or 8 for fr_foveation.levels > 4
+	constexpr uint32_t LV_MASK = (1u << NLV) - 1u, LV_BLEND = 1u << NLV; // a walk's level bits: bit l = a kept tile has int(level) == l, bit NLV = one blends
 	static_assert(!(PACKED && FOV && !LEVELCOL), "the shared-model foveated variant has no packed layout");
 		extern __shared__ __attribute__((aligned(16))) uint32_t lds_hist[];
 	const int lane = threadIdx.x & 63;
@@ -1110,9 +1142,9 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	// (1 << min(max(int(tile_min), 0), 3), | 16 if it blends two levels) -- from the 4-bit table, or from the floats
 #define TILE_FILTER(ti, olim, pass_out, bits_out) do { \
 		if (ldst) { const uint32_t nb_ = (lds_tab[(ti) >> 3] >> (4 * ((ti) & 7))) & 15u; \
-			pass_out = (float)(nb_ & 7u) < (olim); bits_out = (1u << min(nb_ & 7u, 3u)) | ((nb_ & 8u) << 1); } \
+			pass_out = (float)(nb_ & 7u) < (olim); bits_out = (1u << min(nb_ & 7u, 3u)) | (((nb_ & 8u) >> 3) << NLV); } \
 		else { const float lv_ = tile_min[(ti)]; pass_out = lv_ < (olim); \
-			bits_out = pass_out ? ((1u << min(max(f2i(lv_), 0), 3)) | (tile_bl[(ti)] != 0.0f ? 16u : 0u)) : 0u; } } while (0)
+			bits_out = pass_out ? ((1u << min(max(f2i(lv_), 0), NLV - 1)) | (tile_bl[(ti)] != 0.0f ? LV_BLEND : 0u)) : 0u; } } while (0)
 	// Work unit = a "slab" of 64 consecutive items, handled by ONE wave; there is no workgroup
 	// barrier inside the loop (a few near-camera splats make some slabs 100x more expensive than others,
 	// and waiting for the slowest wave of a workgroup at every slab cost a quarter of the kernel).
@@ -1182,7 +1214,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 			if (FOV)
 			{
 #pragma unroll
-				for (int bit = 0; bit < 5; bit++)
+				for (int bit = 0; bit <= NLV; bit++)
 					if (__ballot((m >> bit) & 1u)) bits |= 1u << bit;
 			}
 		}
@@ -1191,10 +1223,10 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	// monotone, so int(min(levels)) == min(int(level)); lowest starts at the Gaussian's own level
 	auto range_from_mask = [&](const uint32_t lvmask, float &lowest, float &highest, bool &be_blend) __attribute__((always_inline))
 	{
-		const int lo_bit = __ffs((int)(lvmask & 15u)) - 1, hi_bit = 31 - __clz((int)(lvmask & 15u));
+		const int lo_bit = __ffs((int)(lvmask & LV_MASK)) - 1, hi_bit = 31 - __clz((int)(lvmask & LV_MASK));
 		lowest = fminf(lowest, (float)lo_bit);
 		highest = fmaxf(highest, (float)hi_bit);
-		be_blend = (lvmask & 16u) != 0;
+		be_blend = (lvmask & LV_BLEND) != 0;
 	};
 	// what the item leaves behind: FR_ITEM_NONE or its level range (RF rasterizer_impl.cu:374-381)
 	auto range_word = [&](const uint32_t count, const float lowest, const float highest, const bool be_blend) __attribute__((always_inline))
@@ -1203,7 +1235,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		if (!FOV) return 0u;
 		const int lo = f2i(lowest);
 		int hi = f2i(highest);
-		if (be_blend) hi = min(hi + 1, FR_FOV_LEVELS - 1);
+		if (be_blend) hi = min(hi + 1, a.levels - 1);
 		return (uint32_t)(lo & 0xff) | ((uint32_t)(hi & 0xff) << 8);
 	};
 	float4 *const orec = s_orec + 4 * (threadIdx.x & ~63);
@@ -1302,14 +1334,14 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 			uint32_t lb;
 			TILE_FILTER(ti, hl + 1, keep, lb);
 			// (int(lowest) / int(highest) are all that is used of them: the level's integer part stands for the level)
-			if (keep) { const float level = (float)(31 - __clz((int)(lb & 15u))); lowest = level; highest = level; be_blend = (lb & 16u) != 0u; }
+			if (keep) { const float level = (float)(31 - __clz((int)(lb & LV_MASK))); lowest = level; highest = level; be_blend = (lb & LV_BLEND) != 0u; }
 		}
 		if (keep) { BUMP_TILE(ti); count = 1; }
 	}
 	// everything else: wave-balanced pair loop
 	bool deferred = false;
 	{
-		uint32_t lvmask = 0; // FOV: bit l = some kept tile has int(level) == l; bit 4 = some kept tile blends
+		uint32_t lvmask = 0; // FOV: bit l = some kept tile has int(level) == l; bit NLV (4) = some kept tile blends
 		// Splats with at least a wave's worth of tiles are walked by the whole wave ONE AT A TIME: the owner is
 		// wave-uniform (scalar registers), so a step needs no owner search and no shuffles and is ~3x shorter
 		// than a step of the mixed loop below. A frame-filling splat is 128 such steps and sits on the
@@ -1405,7 +1437,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 			if (FOV)
 			{
 #pragma unroll
-				for (int bit = 0; bit < 5; bit++)
+				for (int bit = 0; bit <= NLV; bit++)
 					if (__ballot((m >> bit) & 1u) & mine) lvmask |= 1u << bit;
 			}
 		}
@@ -1426,14 +1458,22 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	if (__any(lr != FR_ITEM_NONE))
 	{
 		// (the record this wave made above, put together again from what it kept: not read back through the cache)
-		float4 r[3], lv[FR_FOV_LEVELS];
+		float4 r[3], lv[NLV];
 		r[0] = make_float4(wr[0].x, wr[0].y, fconic.x, fconic.y);
 		r[1] = make_float4(fconic.z, LEVELCOL ? hl : 0.0f, fpos.x, fpos.y);
 		r[2] = make_float4(fpos.z, wr[2].y, (FOV && !LEVELCOL) ? hl : 0.0f, __int_as_float(idx));
 #pragma unroll
-		for (int l = 0; l < FR_FOV_LEVELS; l++) lv[l] = make_float4(0, 0, 0, 0);
+		for (int l = 0; l < NLV; l++) lv[l] = make_float4(0, 0, 0, 0);
 		if (lr != FR_ITEM_NONE) colour_item<VARIANT, PACKED>(a, rows_ok, lr, r, lv);
-		if (LEVELCOL) rows_store<4>(lv, orec, a.geom.lvl + 4 * (size_t)slab * 64, nv, lane);
+		if constexpr (LEVELCOL && NLV == FR_FOV_LEVELS) rows_store<4>(lv, orec, a.geom.lvl + 4 * (size_t)slab * 64, nv, lane);
+		else if constexpr (LEVELCOL)
+		{
+			// eight level rows: the levels 0 .. 3 where a call of four levels keeps them, 4 .. 7 in rows of their own (GeomWS::lvl_hi),
+			// through the same staging rows one after the other
+			const float4 lo4[4] = { lv[0], lv[1], lv[2], lv[3] }, hi4[4] = { lv[4], lv[5], lv[6], lv[7] };
+			rows_store<4>(lo4, orec, a.geom.lvl + 4 * (size_t)slab * 64, nv, lane);
+			rows_store<4>(hi4, orec, a.geom.lvl_hi + 4 * (size_t)slab * 64, nv, lane);
+		}
 		else rows_store<3>(r, orec, a.geom.rec + 3 * (size_t)slab * 64, nv, lane);
 	}
 	} // slab loop
@@ -1470,16 +1510,17 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		}
 		else
 		{
-			float4 r[3], lv[FR_FOV_LEVELS];
+			float4 r[3], lv[NLV];
 #pragma unroll
 			for (int i = 0; i < 3; i++) r[i] = a.geom.rec[3 * (size_t)gitem + i];
 #pragma unroll
-			for (int l = 0; l < FR_FOV_LEVELS; l++) lv[l] = make_float4(0, 0, 0, 0);
+			for (int l = 0; l < NLV; l++) lv[l] = make_float4(0, 0, 0, 0);
 			colour_item<VARIANT, PACKED>(a, rows_ok, lr, r, lv);
 			if (LEVELCOL)
 			{
 #pragma unroll
-				for (int l = 0; l < FR_FOV_LEVELS; l++) a.geom.lvl[(size_t)gitem * FR_FOV_LEVELS + l] = lv[l];
+				for (int l = 0; l < NLV; l++)
+					(l < FR_FOV_LEVELS ? a.geom.lvl : a.geom.lvl_hi)[(size_t)gitem * FR_FOV_LEVELS + (l & 3)] = lv[l];
 			}
 			else { a.geom.rec[3 * (size_t)gitem + 1] = r[1]; a.geom.rec[3 * (size_t)gitem + 2] = r[2]; }
 		}
@@ -1893,7 +1934,19 @@ __global__ void k_pack_cull(int P, const float *means3D, const float *scales, co
 	const float sc[3] = { scales[3 * g], scales[3 * g + 1], scales[3 * g + 2] };
 	out[g] = make_float4(means3D[3 * g], means3D[3 * g + 1], means3D[3 * g + 2], rho_unit(sc, ((const float4 *)rotations)[g]));
 }
-__global__ void k_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out)
+// fr_foveation.levels other than 4 and 8: the caller's opacities [P,L] and shs_dcs [P,L,3] in rows of Lp = 4 or 8 levels (the rest
+// zero), which colour_item fetches as whole 16-byte pieces. One thread per output float of a Gaussian's 4 Lp; coalesced writes.
+__global__ void k_pad_levels(int P, int L, int Lp, const float *opacities, const float *shs_dcs, float *pad_op, float *pad_dc)
+{
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const size_t row = (size_t)4 * Lp;
+	if (i >= (size_t)P * row) return;
+	const size_t g = i / row;
+	const int k = (int)(i - g * row);
+	if (k < Lp) pad_op[g * Lp + k] = k < L ? opacities[g * L + k] : 0.0f;
+	else { const int j = k - Lp; pad_dc[g * 3 * Lp + j] = j < 3 * L ? shs_dcs[g * 3 * L + j] : 0.0f; }
+}
+__global__ void k_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out, int levels)
 {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= (size_t)P * 64) return;
@@ -1904,7 +1957,7 @@ __global__ void k_pack_colour(int P, const float *shs, const float *shs_rest, co
 	{
 		// RF: shs = coefficients 1..15
 		if (k < 45) v = shs[g * 45 + k];
-		else if (k >= 48 && k < 60) v = shs_dcs[g * 12 + (k - 48)];
+		else if (k >= 48 && k < 48 + 3 * levels) v = shs_dcs[g * (size_t)(3 * levels) + (k - 48)];
 	}
 	else if (shs_rest != nullptr) { if (k < 45) v = shs_rest[g * 45 + k]; else if (k < 48) v = shs[g * 3 + (k - 45)]; }
 	else { if (k < 45) v = shs[g * 48 + 3 + k]; else if (k < 48) v = shs[g * 48 + (k - 45)]; }
@@ -1923,10 +1976,10 @@ int launch_pack_cull(int P, const float *means3D, const float *scales, const flo
 	hipLaunchKernelGGL(k_pack_cull, dim3((unsigned)(((size_t)P + 255) / 256)), dim3(256), 0, stream, P, means3D, scales, rotations, (float4 *)out);
 	return check_launch("pack_cull", stream, 0);
 }
-int launch_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out, hipStream_t stream)
+int launch_pack_colour(int P, const float *shs, const float *shs_rest, const float *shs_dcs, float *out, hipStream_t stream, int levels)
 {
 	const size_t n = (size_t)P * 64;
-	hipLaunchKernelGGL(k_pack_colour, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, shs, shs_rest, shs_dcs, out);
+	hipLaunchKernelGGL(k_pack_colour, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, shs, shs_rest, shs_dcs, out, levels);
 	return check_launch("pack_colour", stream, 0);
 }
 
@@ -1938,8 +1991,19 @@ int launch_tile_levels(FwdCtx &c)
 	const fr_forward_args *a = c.a;
 	hipLaunchKernelGGL(k_tile_levels, dim3(((c.gx + FR_LV_PATCH - 1) / FR_LV_PATCH) * ((c.gy + FR_LV_PATCH - 1) / FR_LV_PATCH)), dim3(256), 0, c.stream,
 		c.T, c.gx, c.gy, a->W, a->H, a->gaze_x, a->gaze_y, a->alpha, c.img.tile_lv, c.img.lv_bbox, c.geom.slab_ctr,
-		a->variant == FR_VARIANT_MMFR_PCHECK_OBB ? a->cur_level : -1.0f);
+		a->variant == FR_VARIANT_MMFR_PCHECK_OBB ? a->cur_level : -1.0f, c.fov);
 	return check_launch("tile_levels", c.stream, a->debug);
+}
+
+int launch_pad_levels(FwdCtx &c)
+{
+	const fr_forward_args *a = c.a;
+	if (c.geom.pad_op == nullptr || a->packed_geom) return FR_OK; // (the packed rows are padded already: fr_pack_geom / fr_pack_colour_fov)
+	const int L = c.fov.levels, Lp = padded_levels(L);
+	const size_t n = (size_t)a->P * 4 * Lp;
+	hipLaunchKernelGGL(k_pad_levels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, a->P, L, Lp, a->opacities, a->shs_dcs,
+		c.geom.pad_op, c.geom.pad_dc);
+	return check_launch("pad_levels", c.stream, a->debug);
 }
 
 static PreArgs make_pre_args(FwdCtx &c)
@@ -1955,6 +2019,9 @@ static PreArgs make_pre_args(FwdCtx &c)
 	p.viewmatrix = a->viewmatrix; p.projmatrix = a->projmatrix; p.campos = a->campos;
 	p.packed_geom = a->packed_geom; p.packed_colour = a->packed_colour; p.packed_cull = a->packed_cull;
 	p.shs_dcs = a->shs_dcs; p.highest_levels = a->highest_levels; p.tile_lv = c.img.tile_lv; p.lv_bbox = c.img.lv_bbox; p.T = c.T;
+	p.levels = c.fov.levels;
+	// (fr_foveation.levels other than 4 and 8: the level columns in the library's rows of four / eight, launch_pad_levels)
+	if (c.geom.pad_op != nullptr && !a->packed_geom) { p.opacities = c.geom.pad_op; p.shs_dcs = c.geom.pad_dc; }
 	p.radii = a->radii; p.visibility = c.visibility; p.clear_color = c.fov_split ? a->out_color : nullptr; p.geom = c.geom; p.tile_count = c.img.tile_count; p.hist = c.img.hist; p.raw = a->raw_activations;
 	p.write_cov3D = has_backward(a->variant) ? 1 : 0;
 	p.prefiltered = a->prefiltered;
@@ -2085,7 +2152,12 @@ int launch_bin(FwdCtx &c)
 	switch (a->variant)
 	{
 	case FR_VARIANT_ORIGINAL: LAUNCH_BIN(FR_VARIANT_ORIGINAL); break;
-	case FR_VARIANT_FOV_PCHECK_OBB: LAUNCH_BIN(FR_VARIANT_FOV_PCHECK_OBB); break;
+	case FR_VARIANT_FOV_PCHECK_OBB:
+		if (c.fov.levels <= FR_FOV_LEVELS) LAUNCH_BIN(FR_VARIANT_FOV_PCHECK_OBB);
+		// fr_foveation.levels 5 .. 8: eight level rows per item (no packed instantiation: api.hip refuses the packed tensors)
+		else if (crow) LAUNCH_BIN_PC(FR_VARIANT_FOV8, false, true);
+		else LAUNCH_BIN_PC(FR_VARIANT_FOV8, false, false);
+		break;
 	case FR_VARIANT_MMFR_PCHECK_OBB:      // plain colours + the level filter (on the skip key, see k_tile_levels): the same kernel
 	case FR_VARIANT_NAIVE_FOV_PCHECK_OBB: // (no packed instantiation: validate_forward refuses the packed tensors)
 		if (crow) LAUNCH_BIN_PC(FR_VARIANT_NAIVE_FOV_PCHECK_OBB, false, true); else LAUNCH_BIN_PC(FR_VARIANT_NAIVE_FOV_PCHECK_OBB, false, false);

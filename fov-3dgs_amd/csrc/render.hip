@@ -151,7 +151,9 @@ struct RenderArgs {
 	const uint32_t *point_list; // per-tile sorted lists of ITEMS (positions in vis_list): rec / lvl are per item
 	const uint32_t *vis_list;   // item -> Gaussian index (the training variants' statistics are per Gaussian)
 	const float4 *rec;
-	const float4 *lvl;      // RF
+	const float4 *lvl;      // RF: the items' rows of the levels 0 .. 3
+	const float4 *lvl_hi;   // RF with fr_foveation.levels > 4: ... of the levels 4 .. 7 (else null)
+	float start_blend, blend_width; // RF: fr_foveation (0.5 / 0.5)
 	const float *tile_lv;   // RF float[5][T]
 	const uint32_t *tile_order; // tiles sorted by descending list length (longest first), or null
 	int T;
@@ -567,6 +569,9 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 		// prefetch registers
 		float4 p0 = make_float4(0, 0, 0, 0), pl1 = p0;
 		float2 p1 = make_float2(0, 0);
+		// this wave's level row of every item (wave-uniform: a scalar base address)
+		const int lev = upper ? L2 : L1;
+		const float4 *const lvrow = lev >= FR_FOV_LEVELS ? a.lvl_hi + (lev - FR_FOV_LEVELS) : a.lvl + lev;
 		auto fetch = [&](int e)
 		{
 			const uint32_t id = a.point_list[range.x + e];
@@ -574,7 +579,7 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 			p0 = r[0];
 			const float4 r1 = r[1];
 			p1 = make_float2(r1.x, r1.y);
-			pl1 = a.lvl[(size_t)id * FR_FOV_LEVELS + (upper ? L2 : L1)];
+			pl1 = lvrow[(size_t)id * FR_FOV_LEVELS];
 		};
 		if (lane < n) fetch(lane);
 		int used = 0; // list entries this wave staged for blending (list_consumed)
@@ -702,7 +707,7 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 			if (two_level)
 			{
 				// RF forward.cu:455-470: C1 * w1 + C2 * (1 - w1), w1 = 1 - smoothstep
-				float x = fabsf(est_of(k) - ((float)L1 + 0.5f)) / 0.5f;
+				float x = fabsf(est_of(k) - ((float)L1 + a.start_blend)) / a.blend_width;
 				x = fmaxf(0.0f, fminf(1.0f, x));
 				const float bT = 3 * x * x - 2 * x * x * x;
 				const float w1 = 1 - bT;
@@ -980,7 +985,8 @@ int launch_render(FwdCtx &c)
 	const fr_forward_args *a = c.a;
 	RenderArgs r;
 	r.W = a->W; r.H = a->H; r.gx = c.gx;
-	r.ranges = c.img.ranges; r.point_list = c.bin.point_list; r.vis_list = c.geom.vis_list; r.rec = c.geom.rec; r.lvl = c.geom.lvl;
+	r.ranges = c.img.ranges; r.point_list = c.bin.point_list; r.vis_list = c.geom.vis_list; r.rec = c.geom.rec; r.lvl = c.geom.lvl; r.lvl_hi = c.geom.lvl_hi;
+	r.start_blend = c.fov.start_blend; r.blend_width = c.fov.blend_width;
 	r.tile_lv = c.img.tile_lv; r.tile_order = c.img.tile_order; r.T = c.T; r.bg = a->background; r.out_color = a->out_color;
 	r.final_T = c.img.final_T; r.n_contrib = c.img.n_contrib;
 	r.gaussians_count = a->gaussians_count; r.contributions = a->contributions; r.loss_map = a->loss_map;

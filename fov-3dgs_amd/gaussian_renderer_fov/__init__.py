@@ -5,7 +5,7 @@ import weakref
 
 import torch
 
-from ..diff_gaussian_rasterization_fov_pcheck_obb import GaussianRasterizationSettings, GaussianRasterizer
+from ..diff_gaussian_rasterization_fov_pcheck_obb import FoveationSettings, GaussianRasterizationSettings, GaussianRasterizer  # noqa: F401
 from .. import _native
 from ..rasterizer import PackedModel, _forward_begin, pack_model, serial_frames, visibility_of, zero_points_like
 
@@ -31,12 +31,14 @@ def invalidate_packed(pc):
         pc._fovraster_pack_state = None
 
 
-def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels):
+def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels, foveation=None):
     """The packed layout of a static model (rasterizer.pack_model), made once and kept on the model object.
     A model counts as static when a call hands over the very same tensor objects, unmodified (autograd version
     counters), as the call before it: the second such call packs, later ones reuse. Models whose getters build new
     tensors on every call (activations evaluated per call) never match and render from the ordinary tensors."""
     tensors = (means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels)
+    if foveation is not None and int(FoveationSettings(*foveation).levels) > 4:
+        return None  # (the packed layout has four level slots: more layers render from the ordinary tensors)
     if any(t is None or not t.is_cuda for t in tensors) or (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)):
         return None
     st = getattr(pc, "_fovraster_pack_state", None)
@@ -53,8 +55,12 @@ def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, hig
 
 
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, alpha=None, gazeArray=None,
-           blending=None, starter=None, ender=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None):
+           blending=None, starter=None, ender=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None,
+           foveation=None):
     """Render the scene for one gaze. Background tensor (bg_color) must be on the GPU.
+    foveation (extension): a FoveationSettings -- the layer count L of the composed model (opacities [P,L], shs_dcs [P,L,3]) and
+    the display geometry; None (default) = the reference's constants, exactly today's call. A model whose width does not match is
+    refused.
     packed (extension, opt-in; the image is bit-identical either way): None (default) = render from the ordinary tensors,
     exactly the reference's interface; a rasterizer.PackedModel of this model made by pack_model(); or "auto" = made and
     cached here once the model is seen to be static (_auto_packed: same tensor objects, same storage address, same
@@ -103,7 +109,7 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
     shs_rest = pc.get_rest_features
 
     if isinstance(packed, str):
-        packed = _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels)
+        packed = _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels, foveation)
     if starter is not None:
         starter.record()
     # (successive inference calls overlap on the GPU -- rasterizer.OVERLAP_SUCCESSIVE_FRAMES; a caller that brackets the call with its
@@ -112,7 +118,7 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
         rendered_image, radii = rasterizer(
             means3D=means3D, means2D=means2D, shs_rest=shs_rest, colors_precomp=None, opacities=opacity, scales=scales,
             rotations=rotations, cov3D_precomp=None, shs_dcs=shs_dcs, highest_levels=highest_levels,
-            gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed)
+            gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed, foveation=foveation)
     if ender is not None:
         ender.record()
 
@@ -140,7 +146,7 @@ class PendingRender:
 
 
 def render_begin(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, alpha=None, gazeArray=None,
-                 blending=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None, stream=None):
+                 blending=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None, stream=None, foveation=None):
     """Throughput mode (extension, inference only): enqueue the HEAD of a foveated frame -- tile levels, cull pass, projection,
     tile counts, tile scan -- on `stream` (default: the current one) and return without waiting for its instance count;
     PendingRender.finish() waits for the count and enqueues emission, sort, colours and blend. A host that alternates two
@@ -169,12 +175,12 @@ def render_begin(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=
             scales, rotations = pc.get_scaling, pc.get_rotation
         shs_rest = pc.get_rest_features
         if isinstance(packed, str):
-            packed = _auto_packed(pc, xyz, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels)
+            packed = _auto_packed(pc, xyz, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels, foveation)
         if gazeArray is None:
             raise Exception("gazeArray is required by the foveated rasterizer")
         gaze = gazeArray.detach().flatten().tolist() if isinstance(gazeArray, torch.Tensor) else list(gazeArray)
         empty = torch.Tensor([])
         frame = _forward_begin(_native.VARIANT_FOV_PCHECK_OBB, rs, xyz, shs_rest, empty, opacity, scales, rotations, empty,
                                shs_dcs, highest_levels, (float(gaze[0]), float(gaze[1])), float(alpha), persistent=True,
-                               packed=packed)
+                               packed=packed, foveation=foveation)
         return PendingRender(frame, zero_points_like(xyz))

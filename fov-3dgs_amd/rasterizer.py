@@ -39,6 +39,46 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+class FoveationSettings(NamedTuple):
+    """Layer count and display geometry of the foveated rasterizer (include/fovraster.h: fr_foveation) -- what the reference
+    compiles in (…_fov_pcheck_obb/cuda_rasterizer/auxiliary.h:26-32) and its scripts call --layer_num / --max_pooling_size. The
+    defaults are the reference's constants; `foveation=None` everywhere means exactly those, through the entry points without
+    settings.
+      levels                 L, 2 .. 8: opacities [P,L], shs_dcs [P,L,3], highest_levels in [0, L-1]
+      max_pooling_size       > 1: the largest pooling size in pixels (the level step is (sqrt(max_pooling_size) - 1) / (L - 1))
+      real_image_width       > 0: display width; with real_viewing_distance (> 0, same unit) the field of view the
+      real_viewing_distance       eccentricities are computed for: 2 * atan(width / (2 * distance)), 90 degrees by default
+      start_blend            in (0, 1) and blend_width > 0: where inside a level the blend with the next one starts, and how wide
+                             the smoothstep between them is"""
+    levels: int = 4
+    max_pooling_size: float = 12.0
+    real_image_width: float = 2.0
+    real_viewing_distance: float = 1.0
+    start_blend: float = 0.5
+    blend_width: float = 0.5
+
+
+def _foveation_key(foveation):
+    """-> the settings as a plain tuple (int, five floats), or None for `no settings`"""
+    if foveation is None:
+        return None
+    f = FoveationSettings(*foveation)
+    return (int(f.levels),) + tuple(float(v) for v in f[1:])
+
+
+def _foveation_struct(lib, key):
+    """-> _native.Foveation for fr_forward_begin_fov, or None = the call without settings. A library built before the settings serves
+    only the reference's constants: anything else is refused, never ignored."""
+    if key is None:
+        return None
+    if not _native.has_foveation(lib):
+        if key == _foveation_key(FoveationSettings()):
+            return None
+        raise RuntimeError(f"fovraster: the loaded library ({_native.LIB_PATH}) has no foveation settings (fr_forward_begin_fov): "
+                           f"it renders FoveationSettings() only, not {FoveationSettings(*key)}")
+    return _native.Foveation(C.sizeof(_native.Foveation), *key)
+
+
 def cpu_deep_copy_tuple(input_tuple):
     return tuple(item.cpu().clone() if isinstance(item, torch.Tensor) else item for item in input_tuple)
 
@@ -259,8 +299,9 @@ class PackedModel:
     to the ordinary tensors, which must hold the same values. Forward-only (ignored by the backward pass); the
     image is bit-identical with and without."""
 
-    def __init__(self, geom, colour, cull):
+    def __init__(self, geom, colour, cull, levels=None):
         self.geom, self.colour, self.cull = geom, colour, cull
+        self.levels = levels  # foveated model: the layers it was packed from (FoveationSettings.levels of the calls it serves)
         # the k_pack_* kernels run on the stream that is current now: a frame on another stream waits for them (_Produced)
         self.produced = _Produced(geom.device, (geom, colour, cull)) if geom.is_cuda else None
 
@@ -271,8 +312,9 @@ class PackedModel:
 
 
 def pack_model(means3D, scales, rotations, opacities, shs=None, shs_rest=None, shs_dcs=None, highest_levels=None):
-    """-> PackedModel. opacities [P,1] (or [P,4] per level for the foveated rasterizer, with shs_dcs [P,4,3],
-    highest_levels [P,1] and shs = the 15 rest coefficients); shs [P,16,3], or shs [P,1,3] + shs_rest [P,15,3].
+    """-> PackedModel. opacities [P,1] (or [P,L] per level for the foveated rasterizer, with shs_dcs [P,L,3],
+    highest_levels [P,1] and shs = the 15 rest coefficients; L = FoveationSettings.levels <= 4: the layout has four level
+    slots, the unused ones are zero and never read); shs [P,16,3], or shs [P,1,3] + shs_rest [P,15,3].
     """
     lib = _native.load()
     _require_gpu(means3D)
@@ -281,6 +323,11 @@ def pack_model(means3D, scales, rotations, opacities, shs=None, shs_rest=None, s
     f = lambda t: None if t is None else _f32(t.detach(), dev)
     m, sc, ro, op, sh, rest, dcs, hl = (f(t) for t in (means3D, scales, rotations, opacities, shs, shs_rest, shs_dcs, highest_levels))
     levels = op.numel() // max(P, 1) if P else 1
+    if dcs is not None and P and (dcs.numel() != P * levels * 3 or levels > 4):
+        if levels > 4:
+            raise RuntimeError(f"pack_model: the packed layout holds at most 4 levels, the model has {levels} "
+                               "(render it from the ordinary tensors)")
+        raise RuntimeError(f"pack_model: opacities hold {levels} levels, shs_dcs {dcs.numel() // (3 * P)}")
     geom = torch.empty((P, 16), dtype=torch.float32, device=dev)
     cull = torch.empty((P, 4), dtype=torch.float32, device=dev)
     if sh is None:
@@ -298,10 +345,15 @@ def pack_model(means3D, scales, rotations, opacities, shs=None, shs_rest=None, s
             if ncoef != (15 if dcs is not None else 16):
                 raise RuntimeError(f"pack_model needs all 16 SH coefficients, got {ncoef}")
             colour = torch.empty((P, 64), dtype=torch.float32, device=dev)
-            rc = lib.fr_pack_colour(P, _ptr(sh), _ptr(rest), _ptr(dcs), _ptr(colour), stream)
+            if dcs is not None and levels != 4:  # (a library built before the settings packs four levels only)
+                if not _native.has_foveation(lib):
+                    raise RuntimeError(f"pack_model: the loaded library packs 4-level models only, not {levels} levels")
+                rc = lib.fr_pack_colour_fov(P, _ptr(sh), _ptr(dcs), int(levels), _ptr(colour), stream)
+            else:
+                rc = lib.fr_pack_colour(P, _ptr(sh), _ptr(rest), _ptr(dcs), _ptr(colour), stream)
             if rc != 0:
                 raise RuntimeError(f"fovraster pack_colour failed ({rc}): {_native.last_error()}")
-    return PackedModel(geom, colour, cull)
+    return PackedModel(geom, colour, cull, levels if dcs is not None and P else None)
 
 
 # Set by fov3dgs_amd.profiling.StageTimer while a timed region is active: a ctypes array of
@@ -330,14 +382,17 @@ def visibility_of(radii):
     return vis if vis is not None else radii > 0
 
 
-def _begin_call(lib, a, P, dev, radii, handle):
+def _begin_call(lib, a, P, dev, radii, handle, fov=None):
     """fr_forward_begin with the visibility mask as a second output where the library has it: the mask travels as an attribute of
-    `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object)."""
+    `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object).
+    fov: the call's _native.Foveation (_foveation_struct), or None = today's entry points."""
     if not _native.has_forward_ext(lib):
         return lib.fr_forward_begin(C.byref(a), C.byref(handle))
     vis = torch.empty((P,), dtype=torch.bool, device=dev)  # written in full beside radii, like it
     radii._fovraster_visibility = vis
     ext = _native.ForwardExt(C.sizeof(_native.ForwardExt), vis.data_ptr())  # (read during the call only)
+    if fov is not None:
+        return lib.fr_forward_begin_fov(C.byref(a), C.byref(ext), C.byref(fov), C.byref(handle))
     return lib.fr_forward_begin_ext(C.byref(a), C.byref(ext), C.byref(handle))
 
 
@@ -383,7 +438,7 @@ class FrameInFlight:
 def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                    shs_dcs=None, highest_levels=None, gaze=(0.5, 0.5), alpha=0.05, persistent=False, loss_map=None,
                    sh_rest=None, packed=None, cur_level=0.0, raw_activations=False, list_consumed=None, no_stats=False, blend_pairs=None,
-                   on_stream=None, reuse=None, reuse_key=None):
+                   on_stream=None, reuse=None, reuse_key=None, foveation=None):
     """First half of a forward call on the current stream -> FrameInFlight. on_stream: the caller HAS made this stream (and its
     device) current and says so (saves the lookups). persistent=True: the workspaces are the grow-only
     set of this (device, stream, thread) (valid until the next call there); otherwise they stay reserved for as long as the
@@ -392,7 +447,9 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
     reuse_key -- the caller vouches that every tensor, scalar and flag of the call is what it was at the previous call on that stream, and
     clears the dict whenever a tensor OBJECT changed (the key alone cannot tell a new tensor at a dead one's id and address) --
     the argument struct made then is used again with only the gaze and the two output tensors replaced (filling it is 20 checked
-    tensor arguments: 40 us of host time on a path where the host is the bottleneck)."""
+    tensor arguments: 40 us of host time on a path where the host is the bottleneck). The foveation settings are part of the key
+    (the caller's), and the fr_foveation struct made from them is kept beside the argument struct.
+    foveation (foveated variant): a FoveationSettings, or None = the reference's constants through the entry points without settings."""
     lib = _native.load()
     _require_gpu(means3D)
     dev = means3D.device
@@ -408,12 +465,25 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         a.out_color, a.radii = color.data_ptr(), radii.data_ptr()
         a.stage_events = _stage_events_hook() if _stage_events_hook is not None else None
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle)
+        rc = _begin_call(lib, a, P, dev, radii, handle, reuse["fov"])
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
         return FrameInFlight(lib, a, keep, color, radii, ws, None, None, None, handle, dev, stream)
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    fov_key = _foveation_key(foveation)
+    if fov_key is not None and variant != _native.VARIANT_FOV_PCHECK_OBB:
+        raise RuntimeError("fovraster: foveation settings are for the foveated rasterizer (fov_pcheck_obb) only")
+    if variant == _native.VARIANT_FOV_PCHECK_OBB and P > 0:
+        # the kernels read `levels` columns of every row: a model of another width would be misread without a word
+        levels = 4 if fov_key is None else fov_key[0]
+        for name, t in (("opacities", opacities), ("shs_dcs", shs_dcs)):
+            if t is not None and t.numel() > 0 and (t.dim() < 2 or t.size(1) != levels):
+                raise RuntimeError(f"fovraster: {name} has shape {tuple(t.shape)}: {t.size(1) if t.dim() > 1 else 1} level(s) per Gaussian, but "
+                                   f"the call renders {levels} levels (FoveationSettings.levels; 4 without settings)")
+        if packed is not None and getattr(packed, "levels", None) not in (None, levels):
+            raise RuntimeError(f"fovraster: the packed model was made from {packed.levels} levels, the call renders {levels}")
+    fov = _foveation_struct(lib, fov_key)
     a = _native.ForwardArgs()
     keep = []
 
@@ -496,7 +566,7 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if _stage_events_hook is not None:
             a.stage_events = _stage_events_hook()
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle)
+        rc = _begin_call(lib, a, P, dev, radii, handle, fov)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
     if reuse is not None:
@@ -504,7 +574,7 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if reuse_key is not None and counts is None and lease is None:  # (no per-call outputs beside the image and the radii)
             # (the caller's own tensors are NOT kept: the key vouches that the caller still holds the very objects the pointers
             # belong to; keeping them here would pin a dropped model's gigabytes until the next call)
-            reuse.update(key=reuse_key, a=a, keep=own, ws=ws)
+            reuse.update(key=reuse_key, a=a, keep=own, ws=ws, fov=fov)
     return FrameInFlight(lib, a, keep, color, radii, ws, lease, counts, contribs, handle, dev, stream)
 
 
@@ -620,7 +690,8 @@ def _forward_overlapped(args, kw):
     # argument struct is used again
     rkey = None if outputs else (sig, args[0], int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
                                  int(rs.sh_degree), bool(rs.prefiltered), tuple(sorted((k, v) for k, v in kw.items() if isinstance(v, (int, float, bool)))),
-                                 args[-1] if isinstance(args[-1], float) else None, _packed_key(kw.get("packed")))
+                                 args[-1] if isinstance(args[-1], float) else None, _packed_key(kw.get("packed")),
+                                 _foveation_key(kw.get("foveation")))
     if torch.cuda.current_device() == dev.index:
         torch.cuda.set_stream(own)
         try:
@@ -1106,19 +1177,19 @@ def _make_fov():
     class _RasterizeGaussians(torch.autograd.Function):
         @staticmethod
         def forward(ctx, means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                    raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending, packed=None):
+                    raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending, packed=None, foveation=None):
             args = (variant_id, raster_settings, means3D, shs_rest, colors_precomp, opacities, scales, rotations,
                     cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha))
             if raster_settings.debug:
                 cpu_args = cpu_deep_copy_tuple(args)
                 try:
-                    res = _forward_native(*args, persistent=True, packed=packed)
+                    res = _forward_native(*args, persistent=True, packed=packed, foveation=foveation)
                 except Exception as ex:
                     torch.save(cpu_args, "snapshot_fw.dump")
                     print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                     raise ex
             else:
-                res = _forward_native(*args, persistent=True, packed=packed)
+                res = _forward_native(*args, persistent=True, packed=packed, foveation=foveation)
             num_rendered, color, radii = res[:3]
             ctx.num_rendered = num_rendered
             ctx.mark_non_differentiable(radii)
@@ -1128,20 +1199,21 @@ def _make_fov():
         def backward(ctx, grad_out_color, _):
             # RF/diff_gaussian_rasterization_fov_pcheck_obb/__init__.py:128-187: the foveated extension is
             # inference-only and hands back None for every input
-            return (None,) * 15
+            return (None,) * 16
 
     def rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending,
-                            packed=None):
+                            packed=None, foveation=None):
         if not torch.is_grad_enabled() and not raster_settings.debug:
             # (inference: no graph to build -- the autograd machinery around an inference-only extension is 15 us of host time a
             # frame on a path where the host sets the pace, see OVERLAP_SUCCESSIVE_FRAMES)
             res = _forward_native(variant_id, raster_settings, means3D, shs_rest, colors_precomp, opacities, scales, rotations,
-                                  cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha), persistent=True, packed=packed)
+                                  cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha), persistent=True, packed=packed,
+                                  foveation=foveation)
             return res[1], res[2]
         return _RasterizeGaussians.apply(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                         blending, packed)
+                                         blending, packed, foveation)
 
     class GaussianRasterizer(nn.Module):
         def __init__(self, raster_settings):
@@ -1154,7 +1226,9 @@ def _make_fov():
 
         def forward(self, means3D, means2D, opacities, shs_rest=None, colors_precomp=None, scales=None,
                     rotations=None, cov3D_precomp=None, shs_dcs=None, highest_levels=None, gazeArray=None,
-                    alpha=None, blending=None, packed=None):
+                    alpha=None, blending=None, packed=None, foveation=None):
+            """foveation (extension): a FoveationSettings -- layer count and display geometry --, or None = the reference's
+            constants (4 layers, maximum pooling size 12, a display 2 wide seen from 1, blend band 0.5 / 0.5)."""
             raster_settings = self.raster_settings
             if (shs_rest is None and colors_precomp is None) or (shs_rest is not None and colors_precomp is not None):
                 raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -1169,7 +1243,7 @@ def _make_fov():
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                       blending, packed))
+                                       blending, packed, foveation))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 

@@ -101,14 +101,14 @@ typedef struct fr_forward_args {
 	const float *means3D;        /* [P,3] */
 	const float *shs;            /* [P,M,3] or NULL */
 	const float *colors_precomp; /* [P,3] or NULL */
-	const float *opacities;      /* [P,1]; RF: [P,4] per level */
+	const float *opacities;      /* [P,1]; RF: [P,4] per level ([P,L] with fr_foveation.levels = L) */
 	const float *scales;         /* [P,3] or NULL */
 	const float *rotations;      /* [P,4] or NULL */
 	const float *cov3D_precomp;  /* [P,6] or NULL */
 	const float *viewmatrix;     /* [4,4] as the reference passes it (world-to-camera, transposed) */
 	const float *projmatrix;     /* [4,4] */
 	const float *campos;         /* [3] */
-	const float *shs_dcs;        /* RF: [P,4,3] per-level DC coefficient */
+	const float *shs_dcs;        /* RF: [P,4,3] per-level DC coefficient ([P,L,3] with fr_foveation.levels = L) */
 	const float *highest_levels; /* RF: [P,1] float */
 	/* outputs (caller-allocated; out_color and radii are written in full, they need no initialisation: every pixel by the
 	 * blend -- RF: the two-level tiles, whose two level states are ADDED, are cleared by the cull pass first; no fill command
@@ -288,6 +288,41 @@ typedef struct fr_forward_ext {
 } fr_forward_ext;
 int fr_forward_begin_ext(fr_forward_args *args, const fr_forward_ext *ext, fr_frame **frame);
 int fr_forward_ext_call(fr_forward_args *args, const fr_forward_ext *ext);
+/* Foveation settings of one FR_VARIANT_FOV_PCHECK_OBB call (extension): the layer count and the display geometry the reference
+ * compiles in as `__device__ const`s (…_fov_pcheck_obb/cuda_rasterizer/auxiliary.h:26-32; its scripts' --layer_num /
+ * --max_pooling_size). The defaults are those constants. size = sizeof(fr_foveation) as the caller was compiled; the struct is read
+ * during the call only, and its values travel to the kernels as arguments (no state outlives the call).
+ *   levels                 L, 2 .. 8 (fov_num): opacities is [P,L], shs_dcs [P,L,3], highest_levels holds values in [0, L-1]; a
+ *                          tile's level is capped at float(double(float(L)) - 0.1), a tile blends two levels when
+ *                          frac(tile_min) > start_blend and int(tile_min) < L-1, and a Gaussian's level range ends at
+ *                          min(hi + 1, L-1) when one of its tiles blends.
+ *   max_pooling_size       > 1 (12): the largest pooling size in pixels; the kernels use s = float(sqrt(double(max_pooling_size)))
+ *                          (sqrt_max_ps) and the level step float((double(s) - 1.) / double(float(L-1))), formed once on the host.
+ *   real_image_width       > 0 (2.0): display width; pixels per unit = W / real_image_width.
+ *   real_viewing_distance  > 0 (1.0): the viewer's distance from the display in the same unit: the z component of every view
+ *                          direction and of the pixel distance, and major = (tan(a_max) - tan(a_min)) * real_viewing_distance.
+ *                          Width 2 seen from 1 is a 90 degree field of view.
+ *   start_blend            in (0,1) (0.5) and
+ *   blend_width            > 0 (0.5): the weight of the upper level of a two-level tile is smoothstep(x),
+ *                          x = clamp(|est - (L1 + start_blend)| / blend_width, 0, 1).
+ * fr_forward_begin_fov / fr_forward_fov_call are fr_forward_begin_ext / fr_forward_ext_call with these settings; fov == NULL: the
+ * same calls. A bad struct is FR_ERR_INVALID before anything is enqueued (the message names the field): size too small, levels
+ * outside 2..8, a non-finite or out-of-range value, or settings with another variant (the SMFR / MMFR baselines keep the
+ * reference's constants). levels <= 4 runs the kernels of a call without settings (levels other than 4: the library first copies
+ * the level columns into four-wide rows of its geometry workspace); 5 .. 8 runs a second instantiation of the binning kernel
+ * with eight level rows per item. The geometry workspace depends on levels (fr_geometry_bytes_fov); the image and binning
+ * workspaces and every introspection pointer of the existing entry points do not. */
+typedef struct fr_foveation {
+	uint32_t size;
+	int32_t levels;
+	float max_pooling_size;
+	float real_image_width;
+	float real_viewing_distance;
+	float start_blend;
+	float blend_width;
+} fr_foveation;
+int fr_forward_begin_fov(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **frame);
+int fr_forward_fov_call(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov);
 /* Fill fr_forward_args.packed_geom / packed_colour / packed_cull (device buffers of P*16 / P*64 / P*4 floats) from the tensors of the
  * same names; opacities is [P,levels] with levels = 1 or 4, highest_levels / shs_dcs may be NULL (not RF);
  * shs_rest NULL: shs is [P,16,3] (RF: [P,15,3] = coefficients 1..15 and shs_dcs given), else shs = [P,1,3]. */
@@ -295,6 +330,9 @@ int fr_pack_geom(int32_t P, const float *means3D, const float *scales, const flo
 	int32_t levels, const float *highest_levels, float *packed_geom, void *stream);
 int fr_pack_cull(int32_t P, const float *means3D, const float *scales, const float *rotations, float *packed_cull, void *stream);
 int fr_pack_colour(int32_t P, const float *shs, const float *shs_rest, const float *shs_dcs, float *packed_colour, void *stream);
+/* RF with fr_foveation.levels = 1 .. 4: fr_pack_colour for shs_dcs [P,levels,3] (the missing levels' slots are zero; nobody reads
+ * them). fr_pack_geom takes the level count already. The packed layout has room for four levels: none for levels > 4. */
+int fr_pack_colour_fov(int32_t P, const float *shs, const float *shs_dcs, int32_t levels, float *packed_colour, void *stream);
 int fr_backward(const fr_backward_args *args);
 /* Zero-fill the dense gradient tensors named in `args` (the dL_d* pointers with P, M, shs / shs_rest / colors_precomp as fr_backward
  * would be called; nothing else is read) with one kernel on `fill_stream`; pair with fr_backward_args.outputs_zeroed. No-op for
@@ -552,6 +590,10 @@ int fr_densify_rows(const fr_densify_rows_args *args, void *stream);
 size_t fr_geometry_bytes(int32_t variant, int32_t P);
 size_t fr_image_bytes(int32_t variant, int32_t W, int32_t H);
 size_t fr_binning_bytes(int32_t variant, int64_t num_instances);
+/* fr_geometry_bytes of a call with fr_foveation.levels = `levels` (2 .. 8; 4: the same number; 0 for a bad argument): the rows of
+ * the levels 4 .. 7 and the four-wide copies of the level columns lie BEHIND everything fr_geometry_bytes counts, so every
+ * fr_geometry_* pointer below is where it is without settings. */
+size_t fr_geometry_bytes_fov(int32_t variant, int32_t P, int32_t levels);
 
 /* Introspection for tests: device pointers to internal per-tile / per-instance state inside the workspaces.
  * ranges: uint32 [T,2]. point_list: uint32 [num_rendered], the per-tile depth-sorted lists -- of ITEMS: an item is a
@@ -580,6 +622,9 @@ const float *fr_geometry_walk_records(int32_t variant, int32_t P, const char *ge
  * the levels of the Gaussian's level range are written) and the packed level ranges uint32 [.] = lo | hi << 8 */
 const float *fr_geometry_level_colours(int32_t P, const char *geometry);
 const uint32_t *fr_geometry_level_ranges(int32_t P, const char *geometry);
+/* RF with fr_foveation.levels > 4: the rows of the levels 4 .. 7, float[.][4][4] like fr_geometry_level_colours (which keeps the
+ * levels 0 .. 3); NULL for levels <= 4 */
+const float *fr_geometry_level_colours_hi(int32_t P, int32_t levels, const char *geometry);
 
 #ifdef __cplusplus
 }
