@@ -118,25 +118,54 @@ FULL_FRAME_GRAD_REL_L2 = 2e-5   # whole-tensor relative L2 error of a whole-fram
 FULL_FRAME_GRAD_GROSS = 6e-5    # rows outside 100 x rtol (measured <= 3.3e-5, dL_dopacity)
 
 
-def check_against_noise(got, f32, f64, name, rtol=1e-4, factor=1.5, floor=1e-4):
+def _row_rel(got, want):
+    """Row-relative error ||got_i - want_i|| / ||want_i|| of the rows that carry a gradient (as grad_stats measures it)."""
+    g = np.asarray(got, np.float64).reshape(len(got), -1)
+    w = np.asarray(want, np.float64).reshape(g.shape)
+    rn, dn = np.sqrt((w * w).sum(axis=1)), np.sqrt(((g - w) ** 2).sum(axis=1))
+    live = (rn > 0) | (dn > 0)
+    return dn[live] / np.maximum(rn[live], 1e-300)
+
+
+def check_against_noise(got, f32, f64, name, rtol=1e-4, factor=1.5, floor=1e-4, abs_rows=0.0, tail_floor=5e-6):
     """The HIP gradients `got` and the fp32 restatement of the reference `f32`, both against the same arithmetic in DOUBLE on the same
     forward state (`f64`): the HIP path may leave at most `factor` x the reference arithmetic's own share of rows outside rtol (+ `floor`:
-    rows next to the few (pixel, Gaussian) pairs whose discrete decisions differ between the two forward passes)."""
+    rows next to the few (pixel, Gaussian) pairs whose discrete decisions differ between the two forward passes), and all but 1 % of
+    its rows lie within T = max(2 x the reference arithmetic's 99th percentile, tail_floor).
+    abs_rows: an absolute number of rows BESIDE the fractional allowances, for tensors of a few dozen to a few thousand rows, where
+    the reference's share is two or four rows and the float atomics' order moves a row from run to run: the first clause allows
+    abs_rows more rows outside rtol, the second 1 % of the rows + abs_rows beyond T (the 99th percentile of 50 rows is their
+    largest value, not a property of the bulk), and the share outside 100 x rtol is held to the reference's in the same way
+    (+ 1.5 rows). 0 (the default) leaves the whole-frame comparisons exactly as they were."""
     a, b = grad_stats(got, f64, rtol=rtol), grad_stats(f32, f64, rtol=rtol)
+    n = max(a["rows_with_gradient"], 1)
+    T = max(2.0 * b["row_rel_p99"], tail_floor)
+    beyond = int((_row_rel(got, f64) > T).sum()) if abs_rows > 0 and np.ndim(got) else 0
     parity_report.record("noise", f"{_where()} {name}", hip_vs_f64_frac_bad=a["frac_bad"], ref_f32_vs_f64_frac_bad=b["frac_bad"],
                          hip_vs_f64_p99=a["row_rel_p99"], ref_f32_vs_f64_p99=b["row_rel_p99"], hip_vs_f64_rel_l2=a["rel_l2"], ref_f32_vs_f64_rel_l2=b["rel_l2"],
-                         hip_vs_f64_gross=a["frac_gross"], ref_f32_vs_f64_gross=b["frac_gross"], rows=a["rows_with_gradient"])
+                         hip_vs_f64_gross=a["frac_gross"], ref_f32_vs_f64_gross=b["frac_gross"], rows=a["rows_with_gradient"],
+                         hip_vs_f64_p50=a["row_rel_p50"], ref_f32_vs_f64_p50=b["row_rel_p50"], hip_vs_f64_row_max=a["row_rel_max"],
+                         factor=factor, abs_rows=abs_rows, tail_threshold=T, rows_beyond_tail_threshold=beyond)
     if os.environ.get("FOVRASTER_MEASURE_BUDGETS") == "1":
         return  # calibration run: record, do not judge
-    assert a["frac_bad"] <= factor * b["frac_bad"] + floor, \
+    assert a["frac_bad"] <= factor * b["frac_bad"] + floor + abs_rows / n, \
         f"{name}: {a['frac_bad']:.2e} of the rows outside {rtol:g} of the double-precision gradients; the reference's own fp32 arithmetic: {b['frac_bad']:.2e}"
-    assert a["row_rel_p99"] <= max(2.0 * b["row_rel_p99"], 5e-6), f"{name}: p99 {a['row_rel_p99']:.2e} vs the reference arithmetic's {b['row_rel_p99']:.2e}"
+    if abs_rows > 0:
+        assert beyond <= 0.01 * n + abs_rows, f"{name}: {beyond} of {n} rows beyond {T:.2e} (p99 {a['row_rel_p99']:.2e} vs the reference arithmetic's {b['row_rel_p99']:.2e})"
+        assert a["frac_gross"] <= factor * b["frac_gross"] + floor + 1.5 / n, \
+            f"{name}: {a['frac_gross']:.2e} of the rows outside {100 * rtol:g} of the double-precision gradients; the reference's: {b['frac_gross']:.2e}"
+    else:
+        assert a["row_rel_p99"] <= T, f"{name}: p99 {a['row_rel_p99']:.2e} vs the reference arithmetic's {b['row_rel_p99']:.2e}"
 
 
-def check_grad(got, want, name, rtol=1e-4, outlier_frac=GRAD_OUTLIERS, row_scale=None, cosine=GRAD_COSINE, rel_l2=GRAD_REL_L2, gross_frac=GRAD_GROSS):
+def check_grad(got, want, name, rtol=1e-4, outlier_frac=GRAD_OUTLIERS, row_scale=None, cosine=GRAD_COSINE, rel_l2=GRAD_REL_L2, gross_frac=GRAD_GROSS,
+               min_rows=0):
+    """min_rows: the comparison must judge at least this many rows that carry a gradient (a guard: a change of a scene helper cannot
+    silently shrink a test to a few dozen rows)."""
     st = grad_stats(got, want, rtol=rtol, row_scale=row_scale)
     parity_report.record("grad", f"{_where()} {name}", rtol=rtol, frac_allowed=outlier_frac, gross_allowed=gross_frac, **st)
     assert np.isfinite(got).all(), name
+    assert st["rows_with_gradient"] >= min_rows, f"{name}: only {st['rows_with_gradient']} rows carry a gradient (at least {min_rows} expected)"
     # (a tensor with a few hundred rows may hold three such rows whatever the fraction says)
     assert st["frac_bad"] <= max(outlier_frac, 3.5 / max(st["rows_with_gradient"], 1)), \
         f"{name}: {st['frac_bad']:.2e} of the rows outside {rtol:g} relative (max |diff| {st['max_abs']:.3e})"

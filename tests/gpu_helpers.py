@@ -33,9 +33,11 @@ def vis_list_of(lib, vid, P, geom):
     return _view(geom, lib.fr_geometry_vis_list(vid, P, geom.data_ptr()), n, torch.int32).long()
 
 
-def hip_forward(variant, scene, cam, dev="cuda:0", debug=True, packed=False):
+def hip_forward(variant, scene, cam, dev="cuda:0", debug=True, packed=False, raw=False):
     """-> dict shaped like oracle.forward()'s (the subset the HIP library keeps).
-    packed: also hand the model over in the packed static-model layout (needs scales + rotations + 16 SH coefficients)."""
+    packed: also hand the model over in the packed static-model layout (needs scales + rotations + 16 SH coefficients).
+    raw: scene's scales / rotations / opacities are the model's RAW parameters (fr_forward_args.raw_activations); hip_backward then
+    returns the gradients with respect to them."""
     lib = _native.load()
     vid = VARIANT_IDS[variant]
     rs = settings_from(cam, dev, debug)
@@ -49,13 +51,13 @@ def hip_forward(variant, scene, cam, dev="cuda:0", debug=True, packed=False):
     res = _forward_native(vid, rs, tens["means3D"], tens["shs"], tens["colors_precomp"], tens["opacities"],
                           tens["scales"], tens["rotations"], tens["cov3D_precomp"], tens["shs_dcs"],
                           tens["highest_levels"], cam.get("gaze", (0.5, 0.5)), cam.get("alpha", 0.05),
-                          loss_map=_t(scene.get("loss_map"), dev), packed=pk, cur_level=cam.get("cur_level", 0.0))
+                          loss_map=_t(scene.get("loss_map"), dev), packed=pk, cur_level=cam.get("cur_level", 0.0), raw_activations=raw)
     torch.cuda.synchronize()
     num_rendered, color, radii, geom, binb, img = res[:6]
     W, H = rs.image_width, rs.image_height
     T = ((W + 15) // 16) * ((H + 15) // 16)
     out = {"num_rendered": num_rendered, "color": color.cpu().numpy(), "radii": radii.cpu().numpy(),
-           "_tensors": tens, "_rs": rs, "_buffers": (geom, binb, img), "_radii_t": radii,
+           "_tensors": tens, "_rs": rs, "_buffers": (geom, binb, img), "_radii_t": radii, "_raw": raw,
            "_lease": res[-1]}  # the workspace set stays reserved while this dict lives
     if img.numel() == 0 or tens["means3D"].shape[0] == 0:  # P == 0: the library returns before touching any workspace
         out["ranges"], out["point_list"] = np.zeros((T, 2), np.uint32), np.zeros(0, np.uint32)
@@ -94,7 +96,8 @@ def hip_backward(variant, fwd, dL_dpix, dev="cuda:0"):
                          t["opacities"], t["scales"] if t["scales"] is not None else empty,
                          t["rotations"] if t["rotations"] is not None else empty,
                          t["cov3D_precomp"] if t["cov3D_precomp"] is not None else empty, _t(dL_dpix, dev),
-                         t["shs"] if t["shs"] is not None else empty, geom, fwd["num_rendered"], binb, img, want_cov3D_grad=True, want_color_grad=True)
+                         t["shs"] if t["shs"] is not None else empty, geom, fwd["num_rendered"], binb, img, want_cov3D_grad=True, want_color_grad=True,
+                         raw_activations=fwd.get("_raw", False))
     torch.cuda.synchronize()
     names = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")
     return {n: v.cpu().numpy() for n, v in zip(names, g)}

@@ -5,6 +5,7 @@ session can never overwrite what a GPU session measured (round 3 lost its whole-
   tests/parity_report_cpu.json   everything a session without GPU comparisons recorded (oracle vs golden vectors)
 A session writes them into tests/reports/ (kept out of git, so that a test run leaves the tree as it was), or into the directory
 FOVRASTER_PARITY_REPORT_DIR names (=tests refreshes the committed records)."""
+import contextlib
 import json
 import os
 
@@ -22,6 +23,16 @@ def record(kind, name, **values):
     clean = {k: (float(v) if isinstance(v, (np.floating, float)) else int(v) if isinstance(v, (np.integer, int)) else v)
              for k, v in values.items()}
     _entries.append(dict(kind=kind, name=name, **clean))
+
+
+@contextlib.contextmanager
+def muted():
+    """Comparisons made inside are not kept: for tests that hand a comparison doctored inputs to see it fail."""
+    n = len(_entries)
+    try:
+        yield
+    finally:
+        del _entries[n:]
 
 
 def image_stats(got, want):

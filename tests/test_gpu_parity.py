@@ -154,6 +154,10 @@ def test_max_variant_blends_the_pairs_the_backward_pass_takes():
 
 @pytest.mark.parametrize("variant", ("original", "pcheck_obb_sum"))
 def test_backward_matches_oracle(variant):
+    """small_case saturates within the first few splats of a tile: only 67 (pcheck_obb_sum) / 71 (original) of its 3000 Gaussians
+    carry a gradient, and check_grad's 3.5 / rows lets three of them be off. This test guards the frozen scene of the forward
+    fixtures; the backward pass is judged on thousands of rows, branch by branch, in tests/test_backward_branches_gpu.py.
+    min_rows records today's count as a guard."""
     _need_gpu()
     from tests.gpu_helpers import hip_backward, hip_forward
     scene, cam = small_case(variant)
@@ -164,12 +168,14 @@ def test_backward_matches_oracle(variant):
     got_f = hip_forward(variant, scene, cam)
     got = hip_backward(variant, got_f, dpix)
     for k in ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot"):
-        check_grad(got[k].reshape(want[k].shape), want[k], k)
+        check_grad(got[k].reshape(want[k].shape), want[k], k, min_rows=50)
 
 
 @pytest.mark.parametrize("variant", ("original", "pcheck_obb_sum"))
 def test_backward_with_precomputed_colours_and_covariances(variant):
-    """colors_precomp + cov3D_precomp instead of SH coefficients, scales and rotations (the rasterizer's other input form,
+    """(small_case: about seventy rows carry a gradient; the open scene of tests/test_backward_branches_gpu.py judges this input
+    form on 2970.)
+    colors_precomp + cov3D_precomp instead of SH coefficients, scales and rotations (the rasterizer's other input form,
     diff_gaussian_rasterization/__init__.py:60-75): the backward pass then returns dL_dcolors / dL_dcov3D (backward.cu:346-396 writes
     them either way) and zeros for the tensors of the absent inputs. Every output starts as NaN (tests/conftest.py): positions and
     opacity go out in whole lines, colours and covariances row by row over the fill, scales / rotations are the fill's alone."""
@@ -199,7 +205,8 @@ def test_backward_with_precomputed_colours_and_covariances(variant):
 def test_backward_at_lower_sh_degrees(sh_degree):
     """Active SH degree below the allocated one (early training, scene/gaussian_model.py oneupSHdegree): only the coefficients of
     the active degree are read and get a gradient (backward.cu:20-139), the rest of the [P,16,3] row stays zero -- the path of
-    k_preprocess_bwd that moves a wave's SH rows together handles rows that are only partly used."""
+    k_preprocess_bwd that moves a wave's SH rows together handles rows that are only partly used.
+    (small_case: 67 rows carry a gradient; tests/test_backward_branches_gpu.py runs the degrees on the open scene's 2970.)"""
     _need_gpu()
     from tests.gpu_helpers import hip_backward, hip_forward
     scene, cam = small_case("pcheck_obb_sum")

@@ -42,9 +42,15 @@ def sh_colour(deg, sh, dirs):
     return torch.clamp_min(res + 0.5, 0.0)
 
 
-def rasterize(means3D, scales, rotations, opacities, shs, cam, cutoff=False):
+def rasterize(means3D, scales, rotations, opacities, shs, cam, cutoff=False, detach_clamped_tangents=False):
     """-> image [3,H,W] (float64 in, float64 out). cam: the oracle's camera dict (tests/helpers.cam_dict).
-    cutoff: RS / RP / RF's extra skip of power < -4.5."""
+    cutoff: RS / RP / RF's extra skip of power < -4.5.
+    detach_clamped_tangents: the reference's CONVENTION for a tangent the forward pass clamped (t.x / t.z outside +-1.3 tanfovx,
+    likewise y). The forward value is t.x = +-limx * t.z, which literally depends on t.z; R0 backward.cu:175 / :262-264 zero dL/dt.x
+    (x_grad_mul) yet keep the clamped t.x as a CONSTANT in dL/dt.z (the term 2 h_x t.x tz3 dL_dJ02 -- the literal derivative of
+    -h_x limx / t.z would be half of it). With this switch the clamped t.x / t.y are detached, so that autograd differentiates what
+    the reference's backward does; without it autograd differentiates the forward expression as written, and dL/dmeans3D of the
+    clamped rows differs. The library is a drop-in for the reference: the convention is the contract (tests/test_oracle_pins.py)."""
     f64 = torch.float64
     W, H = int(cam["image_width"]), int(cam["image_height"])
     vm = torch.as_tensor(cam["viewmatrix"], dtype=f64).reshape(4, 4)   # row-major memory of the TRANSPOSED matrix: p_view = p @ vm
@@ -74,6 +80,11 @@ def rasterize(means3D, scales, rotations, opacities, shs, cam, cutoff=False):
     limx, limy = 1.3 * tanx, 1.3 * tany
     txc = torch.minimum(torch.full_like(tz, limx), torch.maximum(torch.full_like(tz, -limx), t[:, 0] / tz)) * tz
     tyc = torch.minimum(torch.full_like(tz, limy), torch.maximum(torch.full_like(tz, -limy), t[:, 1] / tz)) * tz
+    if detach_clamped_tangents:
+        with torch.no_grad():
+            ux, uy = t[:, 0] / tz, t[:, 1] / tz
+            cx, cy = (ux < -limx) | (ux > limx), (uy < -limy) | (uy > limy)
+        txc, tyc = torch.where(cx, txc.detach(), txc), torch.where(cy, tyc.detach(), tyc)
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -(fx * txc) / (tz * tz), zero, fy / tz, -(fy * tyc) / (tz * tz)], 1).reshape(P, 2, 3)
     Wv = vm[:3, :3].T                                                 # world -> camera rotation
