@@ -386,6 +386,31 @@ int fr_l1_ssim_finish(int32_t C, int32_t H, int32_t W, const float *partials, fl
 int fr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const float *target, const float *dmaps, float w_l1, float w_ssim,
 	const float *grad_scale, float *dL_dimg, void *stream);
 
+/* The uniform metameric (HVS) loss, fused (csrc/hvs.hip): MetamericLossUniform with bilinear_downsampling=True and the cropped
+ * 5x5 filters, the loss of metric_mask_learn.py:227 and eff_finetune.py:122. Restated from
+ *   metamer/odak_perception/metameric_loss_uniform.py:8-12 (uniform_blur: area-down by 1/p, bilinear-up), :57-69 (mean, var =
+ *     E[x^2] - mean^2 floored at 1e-7, std), :71-88 (the statistics: h, every band with p halved per level, the last lowpass),
+ *     :90-100 (mean over the statistics of their L1 / MSE mean), :135-156 (the call: the target is detached),
+ *   metamer/odak_perception/spatial_steerable_pyramid.py:6-31 (sizes must be multiples of 2^levels), :132-180 (the pyramid),
+ *   metamer/odak_perception/color_conversion.py:382-404 (RGB -> YCrCb).
+ * img / target: [3,H,W] fp32 device tensors (rgb != 0: converted to YCrCb first). n_levels 2..6, n_orientations 1..8, H and W
+ * multiples of 2^n_levels (else FR_ERR_INVALID), pooling_size > 0, mse != 0: MSE instead of L1.
+ * filters: DEVICE buffer of (2 + n_orientations) * 25 floats = l0, h0, b_0 .. (row-major 5x5, as get_steerable_pyramid_filters(5,
+ *   n, "cropped") returns them). The library holds no coefficients of its own.
+ * fr_hvs_workspace_floats(.., which): floats of 0 = one picture's forward state, 1 = the backward workspace, 2 = the partial
+ *   sums; -1 for bad arguments (fr_last_error says which).
+ * forward:  builds img's state (bands, pooled mean / mean-square per band, lowpasses) in state_img and, unless target is NULL,
+ *   the target's in state_target (NULL: state_target holds that target's state from an earlier call with the same settings);
+ *   compares them and writes the loss to out[0]. The per-workgroup sums in `partials` are added in double in a fixed order.
+ * backward: dL_dimg [3,H,W] = s * d loss / d img, written in full, from the two states of the forward; s = *grad_scale (a
+ *   DEVICE scalar, the upstream gradient) or 1 when grad_scale is NULL. Every sum is a gather: the same bits on every run.
+ * All launches go to `stream`; their number depends on n_levels only. */
+int64_t fr_hvs_workspace_floats(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t which);
+int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+	const float *filters, const float *img, const float *target, float *state_img, float *state_target, float *partials, float *out, void *stream);
+int fr_hvs_backward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+	const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale, float *dL_dimg, void *stream);
+
 /* Mean squared distance of every point to its three nearest neighbours: simple-knn's distCUDA2, the initial scale of
  * GaussianModel.create_from_pcd (replaces SimpleKNN::knn, fov3dgs/submodules/simple-knn/simple_knn.cu:185-220, as called by
  * distCUDA2, spatial.cu:15-25). points: [P,3] fp32 device array; mean_dist2: [P] fp32, written in full:

@@ -1,0 +1,161 @@
+"""The uniform metameric (HVS) loss, fused (fov3dgs_amd.odak_perception.MetamericLossUniform, csrc/hvs.hip) against its torch
+form (tests/hvs_ref.py in float32 on the GPU: the reference's operators, each channel filtered on its own and without the
+reference's host synchronisation per call, so the torch side is if anything flattered), on the MI355X, in ONE process, the two
+candidates alternating call by call, each call between two device events; --warmup rounds, then --steps timed rounds; median,
+p10-p90, min and max in ms:
+  (a) loss + backward at 1088x1920 (the size metric_mask_learn.py / eff_finetune.py resize 1080p to), 5 levels, 6 orientations,
+      L1, pooling 1, 9 and 25; a new target tensor every call, as in the training loops (both pyramids are computed);
+  (b) the mask-learning step as the method runs it: render(masking=True, appearance_only=True) -> bilinear resize to 1088x1920
+      (a torch call in the caller) -> this loss (pooling 9) -> backward -> optim.Adam.step(), on S-6M and S-6M-T, beside the
+      same step with the torch loss.
+The filter coefficients come from tests/golden/ref_hvs.npz. No GPU, no run: there is no fallback.
+
+usage: python tools/hvs_bench.py [--steps 50] [--warmup 10] [--step-rounds 30] [--P 6000000] [--skip-step] [--out profiles/hvs_bench.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import fov3dgs_amd  # noqa: E402,F401
+from fov3dgs_amd import optim  # noqa: E402
+from fov3dgs_amd import synthetic as syn  # noqa: E402
+from fov3dgs_amd.gaussian_renderer import render  # noqa: E402
+from fov3dgs_amd.odak_perception import MetamericLossUniform, _native_hvs  # noqa: E402
+from tests import hvs_ref  # noqa: E402
+
+ARGS = SimpleNamespace(position_lr_init=0.00016, feature_lr=0.0025, opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001)
+W, H = 1920, 1080
+HL, WL = 1088, 1920
+LEVELS, ORIENTATIONS = 5, 6
+VARIANT = "pcheck_obb_sum"
+
+
+class Pipe:
+    debug = False
+
+
+def summary(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
+            "p10_ms": round(sorted(ms)[len(ms) // 10], 4), "p90_ms": round(sorted(ms)[(9 * len(ms)) // 10], 4), "n": len(ms)}
+
+
+def filters():
+    return hvs_ref.filters_from_npz(np.load(os.path.join(ROOT, "tests", "golden", "ref_hvs.npz")), ORIENTATIONS)
+
+
+def candidates(pooling, dev):
+    f = filters()
+    fused = MetamericLossUniform(device=dev, pooling_size=pooling, n_pyramid_levels=LEVELS, n_orientations=ORIENTATIONS, loss_type="L1",
+                                 bilinear_downsampling=True, filters=f)
+    f32 = hvs_ref.filters_to(f, dtype=torch.float32, device=dev)
+    return (("fused", lambda x, t: fused(x, t)), ("torch", lambda x, t: hvs_ref.hvs_loss(x, t, f32, pooling, LEVELS, "L1")))
+
+
+def loss_alone(pooling, dev, a):
+    gen = torch.Generator(device=dev).manual_seed(1)
+    base = torch.rand(1, 3, HL, WL, device=dev, generator=gen)
+    image = (base + 0.05 * torch.randn(1, 3, HL, WL, device=dev, generator=gen)).clamp(0, 1)
+    cands = candidates(pooling, dev)
+    ms, values = {k: [] for k, _ in cands}, {}
+    for it in range(a.warmup + a.steps):
+        evs = []
+        target = base.clone()  # a new tensor every round: nothing is reused from call to call
+        for k, fn in cands:
+            x = image.clone().requires_grad_(True)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            loss = fn(x, target)
+            loss.backward()
+            e1.record()
+            evs.append((k, e0, e1))
+            values[k] = loss.detach()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            for k, e0, e1 in evs:
+                ms[k].append(e0.elapsed_time(e1))
+    st = _native_hvs.Settings(HL, WL, float(pooling), LEVELS, ORIENTATIONS, 0, 1)
+    r = {k: summary(v) for k, v in ms.items()}
+    r["loss"] = {k: float(v) for k, v in values.items()}
+    r["state_bytes_per_picture"] = 4 * _native_hvs.floats(st, 0)
+    r["backward_workspace_bytes"] = 4 * _native_hvs.floats(st, 1)
+    r["fused_faster_beyond_spread"] = bool(r["fused"]["p90_ms"] < r["torch"]["p10_ms"])
+    return r
+
+
+def mask_step(base, cam, bg, dev, a, pooling=9):
+    gen = torch.Generator(device=dev).manual_seed(2)
+    target_pool = [torch.rand(1, 3, HL, WL, device=dev, generator=gen) for _ in range(2)]
+    cands = []
+    for name, fn in candidates(pooling, dev):
+        m = syn.GaussianCloud(*[p.detach().clone() for p in base.parameters()], sh_degree=base.active_sh_degree).requires_grad_(True)
+        cands.append(dict(name=name, fn=fn, model=syn.ReferenceShapedModel(m),
+                          opt=optim.Adam(optim.reference_param_groups(m, ARGS), lr=0.0, eps=1e-15), ms=[]))
+    for it in range(a.warmup + a.step_rounds):
+        evs = []
+        target = target_pool[it % 2].clone()
+        for c in cands:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = render(cam, c["model"], Pipe(), bg, masking=True, cuda_type=VARIANT, appearance_only=True)
+            img = F.interpolate(out["render"].unsqueeze(0), size=(HL, WL), mode="bilinear")
+            c["fn"](img, target).backward()
+            c["opt"].step()
+            c["opt"].zero_grad(set_to_none=True)
+            e1.record()
+            evs.append((c, e0, e1))
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            for c, e0, e1 in evs:
+                c["ms"].append(e0.elapsed_time(e1))
+    r = {"mask_step_" + c["name"] + "_loss": summary(c["ms"]) for c in cands}
+    r["fused_faster_beyond_spread"] = bool(r["mask_step_fused_loss"]["p90_ms"] < r["mask_step_torch_loss"]["p10_ms"])
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--step-rounds", type=int, default=30)
+    ap.add_argument("--P", type=int, default=6_000_000)
+    ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hvs_bench.json"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "hvs_bench needs the MI355X"
+    dev = "cuda:0"
+    result = {"device": torch.cuda.get_device_name(0), "size": [HL, WL], "levels": LEVELS, "orientations": ORIENTATIONS, "loss_type": "L1",
+              "steps": a.steps, "warmup": a.warmup, "torch_form": "tests/hvs_ref.py, float32, grouped convolutions, no host synchronisation",
+              "loss_and_backward": {}, "mask_step": {}}
+    for pooling in (1, 9, 25):
+        r = loss_alone(pooling, dev, a)
+        result["loss_and_backward"][f"pooling_{pooling}"] = r
+        print(json.dumps({f"pooling_{pooling}": r}), flush=True)
+        torch.cuda.empty_cache()
+    if not a.skip_step:
+        cam, bg = syn.camera_ring(0, width=W, height=H).to(dev), torch.zeros(3, device=dev)
+        result["mask_step_rounds"] = a.step_rounds
+        for name, make in (("S-6M", syn.scene_bicycle_scale), ("S-6M-T", syn.scene_translucent)):
+            cloud = make(P=a.P).to(dev)
+            r = mask_step(cloud, cam, bg, dev, a)
+            result["mask_step"][name] = r
+            print(json.dumps({name: r}), flush=True)
+            del cloud
+            torch.cuda.empty_cache()
+    else:
+        result["mask_step"] = "not measured (--skip-step)"
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
