@@ -154,9 +154,10 @@ def decode_u16(q):
     return np.asarray(q).astype(np.float32) / np.float32(65535)
 
 
-def filters_from_npz(z, n_orientations):
-    return {"l0": torch.tensor(z[f"filters{n_orientations}_l0"]), "h0": torch.tensor(z[f"filters{n_orientations}_h0"]),
-            "b": [torch.tensor(b) for b in z[f"filters{n_orientations}_b"]]}
+def filters_from_npz(z, n_orientations, prefix="filters"):
+    """prefix "filters": the reference's own sets (ref_hvs.npz); "afilters": the asymmetric sets of ref_hvs_edges.npz"""
+    return {"l0": torch.tensor(z[f"{prefix}{n_orientations}_l0"]), "h0": torch.tensor(z[f"{prefix}{n_orientations}_h0"]),
+            "b": [torch.tensor(b) for b in z[f"{prefix}{n_orientations}_b"]]}
 
 
 def filters_to(filters, dtype=None, device=None):

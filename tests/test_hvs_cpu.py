@@ -1,5 +1,9 @@
 """The uniform metameric (HVS) loss without a GPU: the float64 restatement (tests/hvs_ref.py) against the reference's own vectors,
-the pooling window / size rules against torch, the argument checks of the public class, and the ABI."""
+the pooling window / size rules against torch, the argument checks of the public class, and the ABI.
+The second fixture (tests/golden/ref_hvs_edges.npz, cases E0 .. E7 listed at EDGE_CASES below) is held to the same rules: what it
+holds, the restatement against the reference's vectors on ph > h levels, one-row and one-column pooled maps and asymmetric
+filters, both kink conditions, the asymmetry of its filter sets, that E2, E4 and E7 SEE a mirrored l0, h0 or band filter where
+the seven cases cannot, and the layout the library plans for them."""
 import os
 import re
 import sys
@@ -197,6 +201,167 @@ def test_workspace_sizes_and_refusals():
     lib = _native.load()
     assert lib.fr_hvs_forward(32, 32, 1.0, 5, 6, 0, 1, None, None, None, None, None, None, None, None) == -1
     assert "null" in _native.last_error()
+
+
+# ---------------------------------------------------------------- the second fixture: ref_hvs_edges.npz (E0 .. E7)
+EDGES = list(range(hc.EDGES))
+#                (H, W, pooling, levels, orientations, type), asymmetric filters
+EDGE_CASES = [((32, 32, 5, 5, 2, "L1"), False),     # E0: level 3 is 4x4 at p = 0.625, pooled 6x6 (ph > h)
+              ((32, 32, 3, 5, 2, "MSE"), False),    # E1: two ph > h levels, 8x8 -> 10x10 and 4x4 -> 10x10
+              ((16, 16, 3, 4, 1, "L1"), True),      # E2: one orientation; ph > h at 4x4 with asymmetric filters
+              ((8, 8, 0.75, 2, 1, "L1"), True),     # E3: p < 1 at level 0, the fewest levels, an image smaller than a tile
+              ((88, 136, 5, 3, 6, "L1"), True),     # E4: tile remainders 8, 8 at level 0 and 12, 4 at level 1 (44x68); p = 5, 2.5
+              ((24, 72, 13, 3, 6, "L1"), True),     # E5: pooled maps of ONE row (1x5 at both levels); RGB and YCrCb
+              ((36, 20, 13, 2, 4, "L1"), True),     # E6: pooled map 2x1, ONE column
+              ((64, 64, 16, 6, 8, "MSE"), True)]    # E7: six levels, eight orientations, identity at the 4x4 last level
+EDGE_SPACES = [(i, "RGB") for i in EDGES] + [(5, "YCrCb")]
+
+
+def _edge_reference(i, colorspace):
+    z, tag = hc.edges(), "" if colorspace == "RGB" else "_ycrcb"
+    return float(z[f"loss_{i}{tag}"]), z[f"grad_{i}{tag}"]
+
+
+def test_edge_fixture_holds_the_eight_cases():
+    z = hc.edges()
+    assert int(z["n"]) == hc.EDGES == len(EDGE_CASES)
+    for i, (want, asym) in enumerate(EDGE_CASES):
+        c = hc.edge_case(i)
+        assert tuple(c[1:7]) == want and c.asymmetric == asym
+        assert [int(v) for v in z[f"mapidx_{i}"]] == hc.edge_map_indices(c.pooling, c.levels, c.orientations)
+        assert z[f"img_{i}"].dtype == np.uint16 == z[f"tgt_{i}"].dtype and z[f"grad_{i}"].dtype == np.float32
+        assert z[f"grad_{i}"].shape == (1, 3, c.H, c.W) == z[f"img_{i}"].shape
+    assert z["grad_5_ycrcb"].shape == z["grad_5"].shape and not np.array_equal(z["grad_5_ycrcb"], z["grad_5"])
+    for no in (1, 4, 6, 8):
+        assert z[f"afilters{no}_b"].shape == (no, 1, 1, 5, 5) and z[f"afilters{no}_b"].dtype == np.float32
+        assert z[f"afilters{no}_l0"].shape == (1, 1, 5, 5) == z[f"afilters{no}_h0"].shape
+    # arrays only: pictures, vectors, filter coefficients, case parameters
+    assert all(v.dtype.kind in "fiu" for v in z.values())
+    for f in ("ref_hvs_edges.npz", "ref_hvs_edges_maps.npz"):
+        assert os.path.getsize(os.path.join(hc.GOLDEN, f)) < (1 << 20)
+
+
+@pytest.mark.parametrize("i,colorspace", EDGE_SPACES)
+def test_restatement_matches_the_reference_on_the_edge_cases(i, colorspace):
+    """test_restatement_matches_the_reference_vectors' bound on the second fixture: it pins the restatement itself on ph > h
+    windows, one-row and one-column maps and (E2 .. E7) on filters whose tap order matters, against the reference's own run"""
+    z, y = hc.edges(), hc.edge_yardstick(i, colorspace)
+    ref_loss, ref_grad = _edge_reference(i, colorspace)
+    rel_loss = abs(ref_loss - y["loss"]) / y["loss"]
+    l2, mx = hc.distances(ref_grad, y["grad"])
+    parity_report.record("hvs", f"reference_vs_float64/E{i}/{colorspace}", rel_loss=rel_loss, grad_rel_l2=l2, grad_max_over_max=mx)
+    print(f"E{i} {colorspace}: reference fp32 vs float64: rel loss {rel_loss:.3e} grad rel L2 {l2:.3e} max/max {mx:.3e}")
+    assert rel_loss < 1e-4 and l2 < 1e-4 and mx < 1e-4
+    if colorspace != "RGB":
+        return
+    idx = [int(v) for v in z[f"mapidx_{i}"]]
+    for name, k in zip(("map0", "mapmid", "mapstd", "maplow"), idx):
+        l2m, mxm = hc.distances(z[f"{name}_{i}"], y["maps"][k])
+        print(f"   {name} (statistic {k}): rel L2 {l2m:.3e} max/max {mxm:.3e}")
+        assert y["maps"][k].shape == z[f"{name}_{i}"].shape
+        assert mxm < 1e-4, (name, mxm)
+
+
+@pytest.mark.parametrize("i,colorspace", EDGE_SPACES)
+def test_edge_inputs_keep_both_kinks_away(i, colorspace):
+    c = hc.edge_case(i)
+    f = hvs_ref.filters_to(hc.filters_of(c), dtype=torch.float64)
+    img, tgt = torch.tensor(c.img, dtype=torch.float64), torch.tensor(c.tgt, dtype=torch.float64)
+    assert hvs_ref.variances_outside_band(img, tgt, f, c.pooling, c.levels, image_colorspace=colorspace) == 0
+    if c.loss_type == "L1":
+        n, share = hvs_ref.undecided_sign_gradient(img, tgt, f, c.pooling, c.levels, image_colorspace=colorspace)
+        print(f"E{i} {colorspace}: {n} statistics differ by less than {hvs_ref.UNDECIDED}, share of the largest gradient {share:.3e}")
+        assert share <= 2e-7  # (the generator's KINK_SHARE)
+        _, ref_grad = _edge_reference(i, colorspace)
+        assert hc.distances(ref_grad, hc.edge_yardstick(i, colorspace)["grad"])[0] < 2e-5  # (the generator's REF_L2)
+
+
+def _blocks(f):
+    return [("l0", f["l0"]), ("h0", f["h0"])] + [(f"b[{k}]", b) for k, b in enumerate(f["b"])]
+
+
+@pytest.mark.parametrize("no", [1, 4, 6, 8])
+def test_asymmetric_filters_differ_from_every_mirror_image(no):
+    """a condition on the fixture: a tap index swapped, flipped or reversed in a kernel changes every one of these filters by at
+    least half its maximum, and no band filter is the negative of its rotation (which |a - b| and the std would not see)"""
+    f = hvs_ref.filters_from_npz(hc.edges(), no, prefix="afilters")
+    assert len(f["b"]) == no
+    for name, a in _blocks(f):
+        a = a.numpy().reshape(5, 5)
+        assert hc.asymmetry(a) >= hc.ASYMMETRY, (name, hc.asymmetry(a))
+        if name != "l0":  # unit L1 norm and no DC gain (make_hvs_edge_golden.py says why); l0 = a unit block + 1/25
+            assert abs(np.abs(a).sum() - 1.0) < 1e-5 and abs(a.sum()) < 1e-6, name
+        else:
+            assert abs(np.abs(a - 1.0 / 25).sum() - 1.0) < 1e-5
+    # and the reference's own sets are what the issue of the second fixture is about: they equal their mirror images
+    g = hc.filters(6)
+    assert hc.asymmetry(g["l0"].numpy()) == 0.0 == hc.asymmetry(g["h0"].numpy())
+    assert all(hc.asymmetry(b.numpy()) < 1e-6 for b in g["b"])
+
+
+def _doctored(f64, which):
+    """a filter set with ONE mistake of the kind a tap index can make"""
+    f = dict(f64, b=list(f64["b"]))
+    if which == "l0 rotated":
+        f["l0"] = torch.flip(f["l0"], (-2, -1))
+    elif which == "h0 transposed":
+        f["h0"] = f["h0"].transpose(-2, -1)
+    else:
+        f["b"][0] = torch.flip(f["b"][0], (-2, -1))
+    return f
+
+
+DOCTORINGS = ["l0 rotated", "h0 transposed", "band 0 rotated"]
+
+
+@pytest.mark.parametrize("which", DOCTORINGS)
+@pytest.mark.parametrize("i", [2, 4, 7])
+def test_the_edge_cases_see_a_wrong_tap_order(i, which):
+    """with ONE filter mirrored (in the forward of both pictures, the backward its transpose) the float64 restatement leaves the
+    yardstick by at least 100 x the allowance the GPU tests grant the library: l0 and h0 in the loss or the gradient; a band
+    rotated by 180 degrees at least in the stored mean map of band 0 ("mapmid")"""
+    c, z, y = hc.edge_case(i), hc.edges(), hc.edge_yardstick(i)
+    got = hc.evaluate(c, _doctored(hvs_ref.filters_to(hc.filters_of(c), dtype=torch.float64), which))
+    ref_loss, ref_grad = _edge_reference(i, "RGB")
+    if which != "band 0 rotated":
+        rel, allow_rel = abs(got["loss"] - y["loss"]) / y["loss"], hc.allowance(abs(ref_loss - y["loss"]) / y["loss"])
+        l2, allow_l2 = hc.distances(got["grad"], y["grad"])[0], hc.allowance(hc.distances(ref_grad, y["grad"])[0])
+        print(f"E{i} {which}: rel loss {rel:.3e} (allowance {allow_rel:.3e}) grad rel L2 {l2:.3e} (allowance {allow_l2:.3e})")
+        assert rel >= 100 * allow_rel or l2 >= 100 * allow_l2
+    else:
+        k = int(z[f"mapidx_{i}"][1])
+        mx, allow = hc.distances(got["maps"][k], y["maps"][k])[1], hc.allowance(hc.distances(z[f"mapmid_{i}"], y["maps"][k])[1])
+        print(f"E{i} {which}: mapmid max/max {mx:.3e} (allowance {allow:.3e})")
+        assert mx >= 100 * allow
+
+
+@pytest.mark.parametrize("which", DOCTORINGS)
+@pytest.mark.parametrize("i", [0, 6])
+def test_the_seven_cases_cannot_see_a_wrong_tap_order(i, which):
+    """the gap the second fixture closes: the same mistakes with the reference's own filters move neither loss nor gradient"""
+    c, y = hc.case(i), hc.yardstick(i)
+    got = hc.evaluate(c, _doctored(hvs_ref.filters_to(hc.filters_of(c), dtype=torch.float64), which))
+    rel, (l2, mx) = abs(got["loss"] - y["loss"]) / y["loss"], hc.distances(got["grad"], y["grad"])
+    print(f"case {i} {which}: rel loss {rel:.3e} grad rel L2 {l2:.3e} max/max {mx:.3e}")
+    assert rel <= 1e-6 and l2 <= 1e-6 and mx <= 1e-6
+
+
+def test_layout_of_the_edge_cases():
+    """ph > h at the levels E0 and E1 are named for, one pooled row for E5, one column for E6 (layout() itself asserts that the
+    Python layout and fr_hvs_workspace_floats agree on the size)"""
+    def lay(i):
+        c = hc.edge_case(i)
+        return _native_hvs.layout(_native_hvs.Settings(c.H, c.W, float(c.pooling), c.levels, c.orientations, int(c.loss_type == "MSE"), 1))
+    e0, e1, e2, e3, e5, e6, e7 = (lay(i) for i in (0, 1, 2, 3, 5, 6, 7))
+    assert not any(v["identity"] for v in e0 + e1 + e2 + e3 + e5 + e6)
+    assert [(v["h"], v["ph"]) for v in e0] == [(32, 6), (16, 6), (8, 6), (4, 6)] and e0[3]["pw"] == 6
+    assert [(v["h"], v["ph"]) for v in e1] == [(32, 10), (16, 10), (8, 10), (4, 10)] and (e1[2]["pw"], e1[3]["pw"]) == (10, 10)
+    assert [(v["h"], v["ph"]) for v in e2] == [(16, 5), (8, 5), (4, 5)]
+    assert [(v["h"], v["w"], v["ph"], v["pw"]) for v in e3] == [(8, 8, 10, 10)]
+    assert [(v["ph"], v["pw"]) for v in e5] == [(1, 5), (1, 5)]
+    assert [(v["h"], v["w"], v["ph"], v["pw"]) for v in e6] == [(36, 20, 2, 1)]
+    assert [v["identity"] for v in e7] == [False, False, False, False, True] and (e7[4]["h"], e7[4]["w"]) == (4, 4)
+    assert (e7[3]["ph"], e7[3]["pw"]) == (4, 4)
 
 
 @pytest.mark.parametrize("i", [i for i in CASES if i not in (2, 4)])

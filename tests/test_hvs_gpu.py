@@ -1,7 +1,13 @@
 """The fused HVS loss (fov3dgs_amd.odak_perception.MetamericLossUniform, csrc/hvs.hip) on the GPU against the float64
 restatement (tests/hvs_ref.py). The allowance of every figure is 3 x the distance of the reference's OWN float32 run
 (tests/golden/ref_hvs.npz) from that yardstick, with a floor of 16 fp32 epsilons (tests/hvs_cases.py); every measured figure,
-the library's and the reference's, is printed and recorded through tests/parity_report.py (kind "hvs")."""
+the library's and the reference's, is printed and recorded through tests/parity_report.py (kind "hvs").
+The test_edge_* tests run the second fixture (tests/golden/ref_hvs_edges.npz, E0 .. E7) under the same rule, each case against
+its own reference vector: E0, E1 pooled maps larger than the band (ph > h: k_hvs_pool, k_hvs_bwd_up's footprints, hvs_g_at's
+window gather), E2 one orientation, E3 pooling 0.75 on a picture smaller than a tile with two levels, E4 tile remainders 8, 8
+and 12, 4, E5 one pooled row (hvs_lerp with n_in = 1) in RGB and YCrCb, E6 one pooled column, E7 six levels and eight
+orientations with a 4x4 identity level. E2 .. E7 use asymmetric filters: a tap index swapped or mirrored in k_hvs_level or
+hvs_convT, which the reference's own symmetric filters hide from the seven cases, moves these results."""
 import gc
 
 import numpy as np
@@ -21,7 +27,7 @@ DEV = "cuda:0"
 
 def _loss_fn(c, **kw):
     return MetamericLossUniform(device=DEV, pooling_size=c.pooling, n_pyramid_levels=c.levels, n_orientations=c.orientations,
-                                loss_type=c.loss_type, bilinear_downsampling=True, filters=hc.filters(c.orientations), **kw)
+                                loss_type=c.loss_type, bilinear_downsampling=True, filters=hc.filters_of(c), **kw)
 
 
 def _run(fn, img_np, tgt_np, colorspace="RGB", upstream=None, dtype=torch.float32):
@@ -189,6 +195,107 @@ def test_ycrcb_path():
                          grad_max_over_max=mx, ref_grad_max_over_max=ref_mx)
     print(f"YCrCb: rel loss {rel:.3e} ({ref_rel:.3e}) grad rel L2 {l2:.3e} ({ref_l2:.3e}) max/max {mx:.3e} ({ref_mx:.3e})")
     assert rel <= hc.allowance(ref_rel) and l2 <= hc.allowance(ref_l2) and mx <= hc.allowance(ref_mx)
+
+
+# ---------------------------------------------------------------- the second fixture: ref_hvs_edges.npz (E0 .. E7)
+EDGES = list(range(hc.EDGES))
+
+
+def _edge_reference(i, colorspace="RGB"):
+    z, tag = hc.edges(), "" if colorspace == "RGB" else "_ycrcb"
+    return float(z[f"loss_{i}{tag}"]), z[f"grad_{i}{tag}"]
+
+
+@pytest.mark.parametrize("i", EDGES)
+def test_edge_loss_and_gradient_match_the_float64_restatement(i):
+    c, y = hc.edge_case(i), hc.edge_yardstick(i)
+    loss, grad = _run(_loss_fn(c), c.img, c.tgt)
+    assert loss.dim() == 0 and loss.device.type == "cuda" and grad.shape == (1, 3, c.H, c.W)
+    _check(f"E{i}", float(loss), grad.cpu().numpy(), y, *_edge_reference(i))
+
+
+@pytest.mark.parametrize("i", EDGES)
+def test_edge_stored_statistic_maps(i):
+    """E0, E1, E2 (and E3) compare a pooled level with ph > h map against map, E5 and E6 a level of one row / one column"""
+    c, z, y = hc.edge_case(i), hc.edges(), hc.edge_yardstick(i)
+    idx = [int(v) for v in z[f"mapidx_{i}"]]
+    got = _library_statistics(c, idx)
+    for name, k in zip(("map0", "mapmid", "mapstd", "maplow"), idx):
+        _, ref_mx = hc.distances(z[f"{name}_{i}"], y["maps"][k])
+        _, mx = hc.distances(got[k], y["maps"][k])
+        parity_report.record("hvs", f"E{i}/{name}", max_over_max=mx, ref_max_over_max=ref_mx)
+        print(f"E{i}/{name} (statistic {k}): max/max {mx:.3e} (reference {ref_mx:.3e})")
+        assert got[k].shape == y["maps"][k].shape
+        assert mx <= hc.allowance(ref_mx), (name, mx, ref_mx)
+
+
+def test_edge_ycrcb_against_its_own_reference_vector():
+    c, y = hc.edge_case(5), hc.edge_yardstick(5, "YCrCb")
+    loss, grad = _run(_loss_fn(c), c.img, c.tgt, colorspace="YCrCb")
+    _check("E5/YCrCb", float(loss), grad.cpu().numpy(), y, *_edge_reference(5, "YCrCb"))
+
+
+@pytest.mark.parametrize("i", [1, 4])
+def test_edge_two_calls_are_bit_identical(i):
+    c = hc.edge_case(i)
+    a = _run(_loss_fn(c), c.img, c.tgt)
+    b = _run(_loss_fn(c), c.img, c.tgt)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+def test_edge_target_state_reuse_never_decides_a_result():
+    """test_target_state_reuse_never_decides_a_result's equalities where the kept state holds pooled maps larger than a band"""
+    c = hc.edge_case(0)
+    fn = _loss_fn(c)
+    img = torch.tensor(c.img, device=DEV)
+    tgt = torch.tensor(c.tgt, device=DEV)
+
+    def run(f, t):
+        x = img.clone().requires_grad_(True)
+        l = f(x, t)
+        l.backward()
+        return l.detach().clone(), x.grad.clone()
+
+    first = run(fn, tgt)
+    assert fn._target is not None and fn._target[0]() is tgt
+    state = fn._target[2]
+    again = run(fn, tgt)
+    assert fn._target[2] is state
+    fresh = run(_loss_fn(c), tgt.clone())
+    assert torch.equal(first[0], again[0]) and torch.equal(first[1], again[1])
+    assert torch.equal(first[0], fresh[0]) and torch.equal(first[1], fresh[1])
+    other = torch.tensor(c.img[:, [2, 0, 1]], device=DEV)
+    tgt.copy_(other)                           # modified in place: the new target's loss
+    changed = run(fn, tgt)
+    assert fn._target[2] is not state
+    want = run(_loss_fn(c), other.clone())
+    assert torch.equal(changed[0], want[0]) and torch.equal(changed[1], want[1])
+    assert not torch.equal(changed[0], first[0])
+
+
+def test_one_loss_object_with_several_settings():
+    """one object (E3's: pooling 0.75, two levels, one orientation) called with E3's pictures (8x8), with E6's (36x20, where its
+    pooled map is 48x26), with E3's again: every result is a fresh object's, bit for bit; the workspace is planned per size"""
+    c3, c6 = hc.edge_case(3), hc.edge_case(6)
+    fn = _loss_fn(c3)
+    small = _run(fn, c3.img, c3.tgt)
+    large = _run(fn, c6.img, c6.tgt)
+    small_again = _run(fn, c3.img, c3.tgt)
+    fresh_small, fresh_large = _run(_loss_fn(c3), c3.img, c3.tgt), _run(_loss_fn(c3), c6.img, c6.tgt)
+    assert small[1].shape == (1, 3, c3.H, c3.W) and large[1].shape == (1, 3, c6.H, c6.W)
+    for got, want in ((small, fresh_small), (large, fresh_large), (small_again, fresh_small)):
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(small[0], large[0])
+
+
+def test_edge_half_precision_image_gets_a_half_gradient():
+    c = hc.edge_case(2)
+    loss, grad = _run(_loss_fn(c), c.img, c.tgt, dtype=torch.float16)
+    assert grad.dtype == torch.float16 and grad.shape == (1, 3, c.H, c.W)
+    img16 = torch.tensor(c.img).half().float().numpy()
+    loss32, grad32 = _run(_loss_fn(c), img16, c.tgt)
+    assert float(loss) == float(loss32)
+    assert torch.equal(grad, grad32.half())
 
 
 def test_three_dimensional_input_and_no_grad():
