@@ -34,6 +34,15 @@
 //                   of the coarser level's lowpass gradient.
 //   k_hvs_bwd_image l0^T of the level-0 lowpass gradient + h0^T of h's gradient, the colour transpose, times the upstream
 //                   gradient (a device scalar).
+// Resized (fr_hvs_*_resized): the scripts resize both pictures bilinearly to the next multiple of 2^levels in front of the loss
+// (metric_mask_learn.py:221-227, eff_finetune.py:116-122, prune.py:128-134: F.interpolate(.., mode='bilinear',
+// align_corners=False); 1080 is no multiple of 32). Here the pictures stay [3,Hs,Ws] and
+//   k_hvs_level<true> samples them in the level-0 load: the staged value at the tile's reflected position (y, x) of the H x W
+//                   grid is the two-tap lerp per axis (hvs_lerp, scale Hs / H, Ws / W) of R, G and B, the colour converted
+//                   afterwards; everything behind the load is the H x W call. k_hvs_level<false> is the kernel as it was.
+//   k_hvs_bwd_resize the transposed resize as a gather per SOURCE pixel over the resized pixels whose own hvs_lerp names it, in
+//                   a fixed order, from k_hvs_bwd_image's H x W gradient in the workspace: no atomics, no zero fill.
+// Hs <= H and Ws <= W only (an axis of equal size is the identity exactly).
 #include "common.h"
 
 namespace fr {
@@ -165,8 +174,15 @@ struct HvsLevelArgs
 	const float *src[2]; float *ws[2];
 	long long low_in, maps, low_out;
 	const float *filt;
+	int hs, wsrc;                                // RESIZED: the pictures are [3,hs,wsrc], sampled at scale ry = hs / h, rx = wsrc / w
+	double ry, rx;
 };
 
+// RESIZED (level 0 only): the staged value at (y, x) of the h x w grid is the bilinear sample (upsample_bilinear2d,
+// align_corners=False: hvs_lerp) of the [3,hs,wsrc] picture, R, G and B interpolated first (in double, kept in fp32) and the
+// colour converted afterwards, as a script that resizes and then calls the loss does. Reflection acts on (y, x). The plain
+// instantiation is the kernel as it was.
+template <bool RESIZED>
 __global__ void __launch_bounds__(256) k_hvs_level(HvsLevelArgs a)
 {
 	__shared__ float S[HVS_IM][HVS_IM + 1], LP[HVS_LP][HVS_LP + 1], F[(2 + HVS_MAXB) * 25];
@@ -182,8 +198,24 @@ __global__ void __launch_bounds__(256) k_hvs_level(HvsLevelArgs a)
 		for (int i = tid; i < HVS_IM * HVS_IM; i += 256)
 		{
 			const int r = i / HVS_IM, c = i - r * HVS_IM;
-			const size_t o = (size_t)hvs_reflect(by + r - 4, h) * w + hvs_reflect(bx + c - 4, w);
 			float v;
+			if (RESIZED)
+			{
+				const HvsLerp ly = hvs_lerp(hvs_reflect(by + r - 4, h), a.ry, a.hs), lx = hvs_lerp(hvs_reflect(bx + c - 4, w), a.rx, a.wsrc);
+				const size_t splane = (size_t)a.hs * a.wsrc;
+				if (a.rgb)
+				{
+					const float R = (float)hvs_bilerp(src, a.wsrc, ly, lx), G = (float)hvs_bilerp(src + splane, a.wsrc, ly, lx),
+						B = (float)hvs_bilerp(src + 2 * splane, a.wsrc, ly, lx);
+					const float Y = 0.299f * R + 0.587f * G + 0.114f * B;
+					v = ch == 0 ? Y : (ch == 1 ? 0.5f + 0.713f * (R - Y) : 0.5f + 0.564f * (B - Y));
+				}
+				else
+					v = (float)hvs_bilerp(src + ch * splane, a.wsrc, ly, lx);
+				S[r][c] = v;
+				continue;
+			}
+			const size_t o = (size_t)hvs_reflect(by + r - 4, h) * w + hvs_reflect(bx + c - 4, w);
 			if (a.rgb)
 			{
 				const float R = src[o], G = src[plane + o], B = src[2 * plane + o];
@@ -548,6 +580,54 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_image(HvsBwdImageArgs a)
 	}
 }
 
+struct HvsBwdResizeArgs { int h, w, hs, wsrc; double ry, rx; const float *g, *gscale; float *dimg; };
+
+// The adjoint of the resized load: dL/d(source) [3,hs,wsrc] from dL/d(resized) g [3,h,w] (k_hvs_bwd_image's output, written
+// WITHOUT the upstream scalar, which multiplies each finished sum here: one rounding per element, so that an upstream gradient
+// scales every element exactly, as in the plain call), a gather: one thread per source pixel, all three channels. The resized
+// rows whose taps can be source row j have src in (j - 1, j + 1), i.e. d in ((j - .5) / ry - .5, (j + 1.5) / ry - .5); one more
+// on each side against rounding, and each candidate's own hvs_lerp (the forward's) decides whether and with what weight it reads
+// row j. Rows, then columns, in ascending order; sums in double, kept in fp32.
+__global__ void __launch_bounds__(256) k_hvs_bwd_resize(HvsBwdResizeArgs a)
+{
+	const int sx = blockIdx.x * 64 + (threadIdx.x & 63), sy = blockIdx.y * 4 + (threadIdx.x >> 6);
+	if (sx >= a.wsrc || sy >= a.hs) return;
+	int ylo = max(0, (int)floor(((double)sy - 0.5) / a.ry - 0.5) - 1), yhi = min(a.h - 1, (int)ceil(((double)sy + 1.5) / a.ry - 0.5) + 1);
+	int xlo = max(0, (int)floor(((double)sx - 0.5) / a.rx - 0.5) - 1), xhi = min(a.w - 1, (int)ceil(((double)sx + 1.5) / a.rx - 0.5) + 1);
+	if (sy == 0) ylo = 0;
+	if (sx == 0) xlo = 0;
+	if (sy == a.hs - 1) yhi = a.h - 1;
+	if (sx == a.wsrc - 1) xhi = a.w - 1;
+	const size_t plane = (size_t)a.h * a.w;
+	double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+	for (int y = ylo; y <= yhi; y++)
+	{
+		const HvsLerp ly = hvs_lerp(y, a.ry, a.hs);
+		const double wy = (ly.i0 == sy ? ly.l0 : 0.0) + (ly.i1 == sy ? ly.l1 : 0.0);
+		if (wy == 0.0) continue;
+		const float *row = a.g + (size_t)y * a.w;
+		for (int x = xlo; x <= xhi; x++)
+		{
+			const HvsLerp lx = hvs_lerp(x, a.rx, a.wsrc);
+			const double wx = (lx.i0 == sx ? lx.l0 : 0.0) + (lx.i1 == sx ? lx.l1 : 0.0);
+			if (wx == 0.0) continue;
+			const double wt = wy * wx;
+			acc0 += wt * (double)row[x]; acc1 += wt * (double)row[plane + x]; acc2 += wt * (double)row[2 * plane + x];
+		}
+	}
+	const size_t splane = (size_t)a.hs * a.wsrc, o = (size_t)sy * a.wsrc + sx;
+	const float s = a.gscale ? *a.gscale : 1.0f;
+	a.dimg[o] = s * (float)acc0; a.dimg[splane + o] = s * (float)acc1; a.dimg[2 * splane + o] = s * (float)acc2;
+}
+
+// a resize of [3,Hs,Ws] to H x W the kernels take: no shrinking on either axis (no script does it; it would need another filter)
+static int hvs_resize_check(int Hs, int Ws, int H, int W)
+{
+	if (Hs <= 0 || Ws <= 0) { set_error("hvs: source size %dx%d is not positive", Hs, Ws); return FR_ERR_INVALID; }
+	if (H < Hs || W < Ws) { set_error("hvs: shrinking %dx%d to %dx%d is unsupported (the resize size must be at least the source size)", Hs, Ws, H, W); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
 static int hvs_group(long long window_elems) { return window_elems <= 16 ? 1 : (window_elems <= 256 ? 8 : 64); }
 
 } // namespace fr
@@ -565,7 +645,8 @@ extern "C" int64_t fr_hvs_workspace_floats(int32_t H, int32_t W, double pooling_
 	return -1;
 }
 
-extern "C" int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+// Hs = 0: img / target are [3,H,W]; else [3,Hs,Ws], resized to H x W in the level-0 load
+static int hvs_forward(int Hs, int Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
 	const float *filters, const float *img, const float *target, float *state_img, float *state_target, float *partials, float *out, void *stream_)
 {
 	HvsPlan p;
@@ -582,7 +663,12 @@ extern "C" int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t
 		a.h = v.h; a.w = v.w; a.nb = p.nb; a.level0 = l == 0; a.rgb = rgb;
 		a.src[0] = img; a.src[1] = target; a.ws[0] = state_img; a.ws[1] = state_target;
 		a.low_in = v.low_in; a.maps = v.maps; a.low_out = v.low_out; a.filt = filters;
-		hipLaunchKernelGGL(k_hvs_level, dim3((v.w + HVS_T - 1) / HVS_T, (v.h + HVS_T - 1) / HVS_T, 3 * nside), dim3(256), 0, stream, a);
+		a.hs = Hs; a.wsrc = Ws; a.ry = Hs ? (double)Hs / (double)H : 1.0; a.rx = Hs ? (double)Ws / (double)W : 1.0;
+		const dim3 grid((v.w + HVS_T - 1) / HVS_T, (v.h + HVS_T - 1) / HVS_T, 3 * nside);
+		if (l == 0 && Hs)
+			hipLaunchKernelGGL(k_hvs_level<true>, grid, dim3(256), 0, stream, a);
+		else
+			hipLaunchKernelGGL(k_hvs_level<false>, grid, dim3(256), 0, stream, a);
 		const size_t plane = (size_t)v.h * v.w;
 		const float wgt = wstat / (float)(3 * plane);
 		if (!v.identity)
@@ -609,7 +695,32 @@ extern "C" int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t
 	return check_launch("hvs_forward", stream, false);
 }
 
-extern "C" int fr_hvs_backward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+extern "C" int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+	const float *filters, const float *img, const float *target, float *state_img, float *state_target, float *partials, float *out, void *stream_)
+{
+	return hvs_forward(0, 0, H, W, pooling_size, n_levels, n_orientations, mse, rgb, filters, img, target, state_img, state_target, partials, out, stream_);
+}
+
+extern "C" int fr_hvs_forward_resized(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations,
+	int32_t mse, int32_t rgb, const float *filters, const float *img, const float *target, float *state_img, float *state_target, float *partials,
+	float *out, void *stream_)
+{
+	int rc = hvs_resize_check(Hs, Ws, H, W);
+	if (rc != FR_OK) return rc;
+	const bool same = Hs == H && Ws == W; // nothing to resize: the plain call
+	return hvs_forward(same ? 0 : Hs, same ? 0 : Ws, H, W, pooling_size, n_levels, n_orientations, mse, rgb, filters, img, target, state_img, state_target,
+		partials, out, stream_);
+}
+
+extern "C" int64_t fr_hvs_resized_backward_floats(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations)
+{
+	HvsPlan p;
+	if (hvs_resize_check(Hs, Ws, H, W) != FR_OK || hvs_plan(H, W, pooling_size, n_levels, n_orientations, &p) != FR_OK) return -1;
+	return p.bwd_floats + ((Hs == H && Ws == W) ? 0 : 3ll * H * W); // the gradient before the resize's adjoint
+}
+
+// Hs = 0: dL_dimg is [3,H,W]; else [3,Hs,Ws], and the workspace holds 3 H W floats more, behind the plain one
+static int hvs_backward(int Hs, int Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
 	const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale, float *dL_dimg, void *stream_)
 {
 	HvsPlan p;
@@ -645,7 +756,33 @@ extern "C" int fr_hvs_backward(int32_t H, int32_t W, double pooling_size, int32_
 		if (l == 0) g0 = a.g;
 	}
 	HvsBwdImageArgs b = {};
-	b.g = g0; b.rgb = rgb; b.filt = filters; b.glow0 = workspace + p.lv[0].glow; b.gscale = grad_scale; b.dimg = dL_dimg;
+	b.g = g0; b.rgb = rgb; b.filt = filters; b.glow0 = workspace + p.lv[0].glow;
+	b.gscale = Hs ? nullptr : grad_scale; // (resized: k_hvs_bwd_resize applies it)
+	b.dimg = Hs ? workspace + p.bwd_floats : dL_dimg;
 	hipLaunchKernelGGL(k_hvs_bwd_image, dim3((W + HVS_T - 1) / HVS_T, (H + HVS_T - 1) / HVS_T, 1), dim3(256), 0, stream, b);
+	if (Hs)
+	{
+		HvsBwdResizeArgs r;
+		r.h = H; r.w = W; r.hs = Hs; r.wsrc = Ws; r.ry = (double)Hs / (double)H; r.rx = (double)Ws / (double)W;
+		r.g = workspace + p.bwd_floats; r.gscale = grad_scale; r.dimg = dL_dimg;
+		hipLaunchKernelGGL(k_hvs_bwd_resize, dim3((Ws + 63) / 64, (Hs + 3) / 4), dim3(256), 0, stream, r);
+	}
 	return check_launch("hvs_backward", stream, false);
+}
+
+extern "C" int fr_hvs_backward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
+	const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale, float *dL_dimg, void *stream_)
+{
+	return hvs_backward(0, 0, H, W, pooling_size, n_levels, n_orientations, mse, rgb, filters, state_img, state_target, workspace, grad_scale, dL_dimg, stream_);
+}
+
+extern "C" int fr_hvs_backward_resized(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations,
+	int32_t mse, int32_t rgb, const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale,
+	float *dL_dimg, void *stream_)
+{
+	int rc = hvs_resize_check(Hs, Ws, H, W);
+	if (rc != FR_OK) return rc;
+	const bool same = Hs == H && Ws == W;
+	return hvs_backward(same ? 0 : Hs, same ? 0 : Ws, H, W, pooling_size, n_levels, n_orientations, mse, rgb, filters, state_img, state_target, workspace,
+		grad_scale, dL_dimg, stream_);
 }

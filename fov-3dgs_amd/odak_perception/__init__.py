@@ -19,19 +19,39 @@ Supported: bilinear_downsampling=True, 5x5 filters, loss_type "L1" / "MSE", [1,3
 is unsupported; a size that is no multiple of 2**n_pyramid_levels raises ValueError as pad_image_for_pyramid does; CPU tensors
 raise (no CPU fallback, as everywhere in this library).
 
+Resize: the steerable pyramid needs a size that is a multiple of 2**n_pyramid_levels, and 1080 is none of 32. ``resize=``
+does what the reference's scripts do with F.interpolate(x, size=.., mode='bilinear', align_corners=False) on both pictures
+before the call (metric_mask_learn.py:221-227, eff_finetune.py:116-122, prune.py:128-134), inside the kernels:
+
+    loss = loss_fn(image, target, resize="pyramid")       # to pyramid_size(H, W, n_pyramid_levels); or resize=(height, width)
+
+``image`` and ``target`` are the un-resized pictures and the gradient has ``image``'s shape. The samples are taken in the load
+of the first pyramid level and the adjoint is a gather per source pixel: no resized picture is written, nothing is added with
+atomics, the same bits on every run. The size may only grow (or stay) on each axis; a size equal to the input's is the plain
+call. Because the caller's own target tensor is what the call sees, the target state below is reusable across steps for a
+caller that keeps its ground truth on the GPU. ``resize=None`` is the call without it, bit for bit.
+
 Target state: the target's pyramid statistics are kept from call to call and reused only when the target is provably the one
 they were computed from -- the same tensor object (held by a weak reference), address, shape, strides and autograd _version,
-the same settings, colour space and device (rasterizer.py's rule for "unchanged"). Anything else recomputes them in the same
+the same settings (the resize size among them), colour space and device (rasterizer.py's rule for "unchanged"). Anything else recomputes them in the same
 launches as the image's. There is no host synchronisation in the call.
 """
 import importlib
+import math
 import weakref
 
 import torch
 
 from . import _native_hvs as _hvs
 
-__all__ = ["MetamericLossUniform"]
+__all__ = ["MetamericLossUniform", "pyramid_size"]
+
+
+def pyramid_size(height, width, n_pyramid_levels):
+    """-> (required_height, required_width): the next multiples of 2**n_pyramid_levels, the size the reference's scripts resize
+    to before the HVS loss (metric_mask_learn.py:188-190, eff_finetune.py:66-68: math.ceil(h / 2**n) * 2**n)"""
+    d = 2 ** n_pyramid_levels
+    return int(math.ceil(height / d) * d), int(math.ceil(width / d) * d)
 
 
 def _load_filters(n_orientations):
@@ -116,7 +136,33 @@ class MetamericLossUniform:
             self._target = None
         return state, True
 
-    def __call__(self, image, target, image_colorspace="RGB", visualise_loss=False):
+    def _resize_size(self, resize, Hs, Ws):
+        """-> (H, W) the loss runs at, or None for the plain call (no resize asked for, or to the pictures' own size)"""
+        if resize is None:
+            return None
+        if isinstance(resize, str):
+            if resize != "pyramid":
+                raise ValueError(f"resize={resize!r} is malformed: None, 'pyramid' or (height, width)")
+            size = pyramid_size(Hs, Ws, self.n_pyramid_levels)
+        else:
+            try:
+                size = tuple(resize)
+            except TypeError:
+                size = ()
+            if len(size) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size):
+                raise ValueError(f"resize={resize!r} is malformed: None, 'pyramid' or (height, width) as two positive ints")
+        if size == (Hs, Ws):
+            return None
+        H, W = size
+        if H < Hs or W < Ws:
+            raise ValueError(f"resize={size}: shrinking a {Hs}x{Ws} picture is unsupported (each side may only grow or stay)")
+        d = 2 ** self.n_pyramid_levels
+        if H % d or W % d:
+            raise ValueError(f"resize={size}: the resize size is no multiple of 2 ** n_pyramid_levels = {d} "
+                             f"(pyramid_size gives {pyramid_size(Hs, Ws, self.n_pyramid_levels)})")
+        return size
+
+    def __call__(self, image, target, image_colorspace="RGB", visualise_loss=False, resize=None):
         if visualise_loss:
             raise NotImplementedError("MetamericLossUniform: visualise_loss is unsupported")
         if image_colorspace not in ("RGB", "YCrCb"):
@@ -132,14 +178,17 @@ class MetamericLossUniform:
             raise NotImplementedError(f"MetamericLossUniform: only 3-channel [1,3,H,W] / [3,H,W] input is supported, got {shape} "
                                       "(1-channel input is unsupported)")
         H, W = shape[-2], shape[-1]
+        size = self._resize_size(resize, H, W)
         d = 2 ** self.n_pyramid_levels
-        if H % d or W % d:
+        if size is None and (H % d or W % d):
             raise ValueError("Please make the image size valid (Multiplies of 2 ** n_pyramid_levels) before input to HVS function.")
         if not (image.is_cuda and target.is_cuda):
             raise RuntimeError("MetamericLossUniform needs GPU tensors: there is no CPU fallback")
         if image.device != target.device:
             raise RuntimeError(f"image is on {image.device}, target on {target.device}")
         st = self._settings(H, W, image_colorspace == "RGB")
+        if size is not None:  # the pictures are H x W and the loss runs at `size`
+            st = st._replace(H=size[0], W=size[1], Hs=H, Ws=W)
         tgt = target.detach().reshape(3, H, W)
         if tgt.dtype != torch.float32 or not tgt.is_contiguous():
             tgt = tgt.float().contiguous()

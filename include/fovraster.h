@@ -411,6 +411,27 @@ int fr_hvs_forward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, 
 int fr_hvs_backward(int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb,
 	const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale, float *dL_dimg, void *stream);
 
+/* The same loss of pictures that are first resized to the pyramid's size, the resize inside the kernels: what
+ * F.interpolate(x, size=(H, W), mode='bilinear', align_corners=False) followed by the calls above computes
+ * (metric_mask_learn.py:221-227, eff_finetune.py:116-122, prune.py:128-134), with no resized picture in memory and no atomics.
+ * img / target: [3,Hs,Ws] fp32 device tensors. H, W: the size the loss runs at, multiples of 2^n_levels; Hs <= H and Ws <= W
+ *   (a smaller H or W -- shrinking -- is FR_ERR_INVALID; an axis of equal size is the identity exactly; Hs == H and Ws == W is
+ *   the plain call). Every other argument is fr_hvs_forward's / fr_hvs_backward's.
+ * forward_resized:  the level-0 load samples the pictures bilinearly (src = (Hs / H) (y + .5) - .5, negative -> 0, the second tap
+ *   clamped at the last row / column; R, G and B are interpolated, in double and kept in fp32, then the colour is converted).
+ *   state_img / state_target / partials have the layout and sizes of the H x W call (fr_hvs_workspace_floats(H, W, ..)).
+ * backward_resized: dL_dimg [3,Hs,Ws] = s * d loss / d img, written in full: the H x W gradient goes to the workspace and a
+ *   gather per SOURCE pixel applies the transposed resize (weights added in ascending row, then column order: the same bits on
+ *   every run). workspace: fr_hvs_resized_backward_floats(..) floats = the plain backward workspace + 3 H W (+ 0 when nothing
+ *   is resized); -1 for bad arguments (fr_last_error says which). One launch more than fr_hvs_backward. */
+int fr_hvs_forward_resized(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations,
+	int32_t mse, int32_t rgb, const float *filters, const float *img, const float *target, float *state_img, float *state_target, float *partials,
+	float *out, void *stream);
+int fr_hvs_backward_resized(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations,
+	int32_t mse, int32_t rgb, const float *filters, const float *state_img, const float *state_target, float *workspace, const float *grad_scale,
+	float *dL_dimg, void *stream);
+int64_t fr_hvs_resized_backward_floats(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations);
+
 /* Mean squared distance of every point to its three nearest neighbours: simple-knn's distCUDA2, the initial scale of
  * GaussianModel.create_from_pcd (replaces SimpleKNN::knn, fov3dgs/submodules/simple-knn/simple_knn.cu:185-220, as called by
  * distCUDA2, spatial.cu:15-25). points: [P,3] fp32 device array; mean_dist2: [P] fp32, written in full:

@@ -8,9 +8,20 @@ p10-p90, min and max in ms:
   (b) the mask-learning step as the method runs it: render(masking=True, appearance_only=True) -> bilinear resize to 1088x1920
       (a torch call in the caller) -> this loss (pooling 9) -> backward -> optim.Adam.step(), on S-6M and S-6M-T, beside the
       same step with the torch loss.
+and, from pictures of 1080x1920 as the scripts hold them (section "resized" of the result), the resize the parent of this
+keyword left to the caller against the resize inside the kernels, the same protocol:
+  (a') loss + backward at pooling 9, a new target tensor every round: interpolate_then_fused (F.interpolate of both pictures to
+       1088x1920, the fused loss, backward through both) against fused_resize (resize="pyramid");
+  (b') the mask-learning step on S-6M with targets at 1080x1920 in the same two forms, and fused_resize_fixed_target: one target
+       object held across the rounds, whose pyramid state the loss object then reuses (a caller with its ground truth on the GPU);
+  per form torch.cuda.max_memory_allocated of one step above what was allocated before it, and whether the image gradient of
+  two identical rounds is the same bits (torch lists upsample_bilinear2d_backward as non-deterministic; ours is a gather).
+  fused_resize_not_slower_beyond_spread: fused_resize's p10 does not lie above interpolate_then_fused's p90.
 The filter coefficients come from tests/golden/ref_hvs.npz. No GPU, no run: there is no fallback.
 
-usage: python tools/hvs_bench.py [--steps 50] [--warmup 10] [--step-rounds 30] [--P 6000000] [--skip-step] [--out profiles/hvs_bench.json]"""
+usage: python tools/hvs_bench.py [--steps 50] [--warmup 10] [--step-rounds 30] [--P 6000000] [--skip-step] [--resized-only]
+                                 [--out profiles/hvs_bench.json]
+--resized-only measures the section "resized" alone and keeps the other sections of an existing --out file as they are."""
 import argparse
 import json
 import os
@@ -121,6 +132,131 @@ def mask_step(base, cam, bg, dev, a, pooling=9):
     return r
 
 
+def resize_forms(pooling, dev):
+    """(name, fn(image [3,H,W] requiring grad, target [3,H,W]) -> loss): the two ways to the loss from 1080x1920 pictures"""
+    def make():
+        return MetamericLossUniform(device=dev, pooling_size=pooling, n_pyramid_levels=LEVELS, n_orientations=ORIENTATIONS, loss_type="L1",
+                                    bilinear_downsampling=True, filters=filters())
+    before, inside = make(), make()
+
+    def interpolate_then_fused(x, t):  # metric_mask_learn.py:221-227
+        t = F.interpolate(t.unsqueeze(0), size=(HL, WL), mode="bilinear", align_corners=False)
+        x = F.interpolate(x.unsqueeze(0), size=(HL, WL), mode="bilinear", align_corners=False)
+        return before(x, t)
+
+    def fused_resize(x, t):  # t itself, not a view of it: the target state is keyed by the object
+        return inside(x, t, resize="pyramid")
+
+    fused_resize.loss_object = inside
+    return (("interpolate_then_fused", interpolate_then_fused), ("fused_resize", fused_resize))
+
+
+def peak_bytes(step):
+    """torch.cuda.max_memory_allocated of one call of step() above what was allocated before it"""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    step()
+    torch.cuda.synchronize()
+    return int(torch.cuda.max_memory_allocated() - base)
+
+
+def resized_loss_alone(dev, a, pooling=9):
+    gen = torch.Generator(device=dev).manual_seed(3)
+    base = torch.rand(3, H, W, device=dev, generator=gen)
+    image = (base + 0.05 * torch.randn(3, H, W, device=dev, generator=gen)).clamp(0, 1)
+    forms = resize_forms(pooling, dev)
+    ms, values, grads = {k: [] for k, _ in forms}, {}, {k: [] for k, _ in forms}
+
+    def step(fn, target):
+        x = image.clone().requires_grad_(True)
+        loss = fn(x, target)
+        loss.backward()
+        return loss, x.grad
+
+    for it in range(a.warmup + a.steps):
+        evs = []
+        target = base.clone()  # a new tensor every round
+        for k, fn in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            loss, grad = step(fn, target)
+            e1.record()
+            evs.append((k, e0, e1))
+            values[k] = loss.detach()
+            if it < 2:
+                grads[k].append(grad.clone())
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            for k, e0, e1 in evs:
+                ms[k].append(e0.elapsed_time(e1))
+    r = {k: summary(v) for k, v in ms.items()}
+    r["loss"] = {k: float(v) for k, v in values.items()}
+    r["image_gradient_of_two_identical_rounds_equal"] = {k: bool(torch.equal(*g)) for k, g in grads.items()}
+    r["peak_bytes_of_one_step"] = {k: peak_bytes(lambda fn=fn: step(fn, base.clone())) for k, fn in forms}
+    r["fused_resize_not_slower_beyond_spread"] = bool(r["fused_resize"]["p10_ms"] <= r["interpolate_then_fused"]["p90_ms"])
+    return r
+
+
+def resized_mask_step(base, cam, bg, dev, a, pooling=9):
+    gen = torch.Generator(device=dev).manual_seed(4)
+    target_pool = [torch.rand(3, H, W, device=dev, generator=gen) for _ in range(2)]
+    fixed = target_pool[0].clone()
+    forms = list(resize_forms(pooling, dev))
+    forms.append(("fused_resize_fixed_target", resize_forms(pooling, dev)[1][1]))  # a loss object of its own: its state is its own
+    cands = []
+    for name, fn in forms:
+        m = syn.GaussianCloud(*[p.detach().clone() for p in base.parameters()], sh_degree=base.active_sh_degree).requires_grad_(True)
+        cands.append(dict(name=name, fn=fn, model=syn.ReferenceShapedModel(m),
+                          opt=optim.Adam(optim.reference_param_groups(m, ARGS), lr=0.0, eps=1e-15), ms=[]))
+
+    def step(c, target):
+        out = render(cam, c["model"], Pipe(), bg, masking=True, cuda_type=VARIANT, appearance_only=True)
+        c["fn"](out["render"], target).backward()
+        c["opt"].step()
+        c["opt"].zero_grad(set_to_none=True)
+
+    for it in range(a.warmup + a.step_rounds):
+        evs = []
+        target = target_pool[it % 2].clone()
+        for c in cands:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step(c, fixed if c["name"].endswith("fixed_target") else target)
+            e1.record()
+            evs.append((c, e0, e1))
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            for c, e0, e1 in evs:
+                c["ms"].append(e0.elapsed_time(e1))
+    r = {"mask_step_" + c["name"]: summary(c["ms"]) for c in cands}
+    held = cands[2]["fn"].loss_object._target  # the fixed target's state must be the one object from the first round on
+    state_ptr = held[2].data_ptr()
+    step(cands[2], fixed)
+    r["fixed_target_state_reused"] = bool(cands[2]["fn"].loss_object._target[2].data_ptr() == state_ptr and held[0]() is fixed)
+    r["peak_bytes_of_one_step"] = {c["name"]: peak_bytes(lambda c=c: step(c, fixed if c["name"].endswith("fixed_target") else target_pool[1]))
+                                   for c in cands}
+    r["fused_resize_not_slower_beyond_spread"] = bool(r["mask_step_fused_resize"]["p10_ms"] <= r["mask_step_interpolate_then_fused"]["p90_ms"])
+    return r
+
+
+def resized(dev, a):
+    r = {"source_size": [H, W], "pooling": 9, "loss_and_backward": resized_loss_alone(dev, a)}
+    print(json.dumps({"resized_loss_and_backward": r["loss_and_backward"]}), flush=True)
+    torch.cuda.empty_cache()
+    if not a.skip_step:
+        cam, bg = syn.camera_ring(0, width=W, height=H).to(dev), torch.zeros(3, device=dev)
+        cloud = syn.scene_bicycle_scale(P=a.P).to(dev)
+        r["mask_step"] = {"S-6M": resized_mask_step(cloud, cam, bg, dev, a)}
+        r["mask_step_rounds"] = a.step_rounds
+        print(json.dumps({"resized_mask_step": r["mask_step"]}), flush=True)
+        del cloud
+        torch.cuda.empty_cache()
+    else:
+        r["mask_step"] = "not measured (--skip-step)"
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -128,10 +264,19 @@ def main():
     ap.add_argument("--step-rounds", type=int, default=30)
     ap.add_argument("--P", type=int, default=6_000_000)
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--resized-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hvs_bench.json"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "hvs_bench needs the MI355X"
     dev = "cuda:0"
+    if a.resized_only:
+        with open(a.out) as fh:
+            result = json.load(fh)
+        result["resized"] = dict(resized(dev, a), steps=a.steps, warmup=a.warmup)
+        with open(a.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+        return
     result = {"device": torch.cuda.get_device_name(0), "size": [HL, WL], "levels": LEVELS, "orientations": ORIENTATIONS, "loss_type": "L1",
               "steps": a.steps, "warmup": a.warmup, "torch_form": "tests/hvs_ref.py, float32, grouped convolutions, no host synchronisation",
               "loss_and_backward": {}, "mask_step": {}}
@@ -152,6 +297,7 @@ def main():
             torch.cuda.empty_cache()
     else:
         result["mask_step"] = "not measured (--skip-step)"
+    result["resized"] = dict(resized(dev, a), steps=a.steps, warmup=a.warmup)
     with open(a.out, "w") as fh:
         json.dump(result, fh, indent=1)
         fh.write("\n")
