@@ -155,7 +155,8 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_forward_begin_ext", "fr_forward_ext_call", "fr_backward_appearance",
            "fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov",
            "fr_hvs_workspace_floats", "fr_hvs_forward", "fr_hvs_backward",
-           "fr_hvs_forward_resized", "fr_hvs_backward_resized", "fr_hvs_resized_backward_floats")
+           "fr_hvs_forward_resized", "fr_hvs_backward_resized", "fr_hvs_resized_backward_floats",
+           "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -231,6 +232,13 @@ def load():
     lib.fr_hvs_backward_resized.restype = C.c_int
     lib.fr_hvs_resized_backward_floats.argtypes = [C.c_int32] * 4 + [C.c_double, C.c_int32, C.c_int32]
     lib.fr_hvs_resized_backward_floats.restype = C.c_int64
+    lib.fr_hvs_fov_workspace_floats.argtypes = [C.c_int32] * 7
+    lib.fr_hvs_fov_workspace_floats.restype = C.c_int64
+    _fov = [C.c_int32] * 4 + [C.c_double] * 3 + [C.c_int32, C.c_double, C.c_double] + [C.c_int32] * 4
+    lib.fr_hvs_fov_forward.argtypes = _fov + [_FP] * 6 + [C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_hvs_fov_forward.restype = C.c_int
+    lib.fr_hvs_fov_backward.argtypes = _fov + [_FP] * 7 + [C.c_void_p]
+    lib.fr_hvs_fov_backward.restype = C.c_int
     for n in ("fr_geometry_bytes",):
         getattr(lib, n).argtypes = [C.c_int32, C.c_int32]
         getattr(lib, n).restype = C.c_size_t

@@ -43,16 +43,11 @@
 //   k_hvs_bwd_resize the transposed resize as a gather per SOURCE pixel over the resized pixels whose own hvs_lerp names it, in
 //                   a fixed order, from k_hvs_bwd_image's H x W gradient in the workspace: no atomics, no zero fill.
 // Hs <= H and Ws <= W only (an axis of equal size is the identity exactly).
-#include "common.h"
+// The foveated loss (csrc/hvs_fov.hip) launches k_hvs_level, k_hvs_bwd_level<FOV>, k_hvs_bwd_image<FOV>, k_hvs_bwd_resize,
+// k_hvs_cmp_direct and k_hvs_finish through the launchers at the end of the namespace; hvs_common.h holds what both files share.
+#include "hvs_common.h"
 
 namespace fr {
-
-#define HVS_T 16
-#define HVS_LP (HVS_T + 4)
-#define HVS_IM (HVS_T + 8)
-#define HVS_MAXB 8
-#define HVS_MAXL 6
-#define HVS_VAR_FLOOR 1e-7
 
 struct HvsLevel
 {
@@ -114,70 +109,7 @@ static int hvs_plan(int H, int W, double pooling, int L, int nb, HvsPlan *p)
 	return FR_OK;
 }
 
-// ---------------------------------------------------------------- device helpers
-__device__ __forceinline__ int hvs_reflect(int i, int n)
-{
-	if (i < 0) i = -i;
-	if (i >= n) i = 2 * (n - 1) - i;
-	return min(max(i, 0), n - 1); // (only positions no output uses get here out of range)
-}
-
-struct HvsLerp { int i0, i1; double l0, l1; };
-
-// upsample_bilinear2d, align_corners=False: src = scale (d + .5) - .5, negative -> 0
-__device__ __forceinline__ HvsLerp hvs_lerp(int d, double scale, int n_in)
-{
-	double src = scale * ((double)d + 0.5) - 0.5;
-	if (src < 0.0) src = 0.0;
-	HvsLerp r;
-	r.i0 = min((int)src, n_in - 1);
-	r.i1 = r.i0 + (r.i0 < n_in - 1 ? 1 : 0);
-	r.l1 = src - (double)r.i0; r.l0 = 1.0 - r.l1;
-	return r;
-}
-
-__device__ __forceinline__ double hvs_bilerp(const float *__restrict__ a, int pw, const HvsLerp &y, const HvsLerp &x)
-{
-	return y.l0 * (x.l0 * (double)a[y.i0 * pw + x.i0] + x.l1 * (double)a[y.i0 * pw + x.i1])
-		+ y.l1 * (x.l0 * (double)a[y.i1 * pw + x.i0] + x.l1 * (double)a[y.i1 * pw + x.i1]);
-}
-
-// The statistics are evaluated in double (gfx950 runs vector fp64 at the fp32 rate; these kernels wait for memory): the L1 loss
-// takes sign(a - b) of two statistics that can differ by less than an fp32 evaluation resolves (the reference's fp32 statistics
-// are ~3e-9 rms off the float64 ones), and ONE flipped sign moves dL/dimage by ~1e-3 of its maximum.
-struct HvsStat { double mean, std, var; };
-
-__device__ __forceinline__ HvsStat hvs_stat(const float *__restrict__ pm, const float *__restrict__ pq, int pw, const HvsLerp &y, const HvsLerp &x)
-{
-	HvsStat s;
-	s.mean = hvs_bilerp(pm, pw, y, x);
-	s.var = hvs_bilerp(pq, pw, y, x) - s.mean * s.mean;
-	s.std = sqrt(s.var < HVS_VAR_FLOOR ? HVS_VAR_FLOOR : s.var);
-	return s;
-}
-
-__device__ __forceinline__ float hvs_dabs(double d, int mse) { return mse ? (float)(2.0 * d) : (d > 0.0 ? 1.0f : (d < 0.0 ? -1.0f : 0.0f)); }
-
-__device__ __forceinline__ double hvs_block_sum(double v, double *s_red)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-	if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-
 // ---------------------------------------------------------------- forward
-struct HvsLevelArgs
-{
-	int h, w, nb, level0, rgb;
-	const float *src[2]; float *ws[2];
-	long long low_in, maps, low_out;
-	const float *filt;
-	int hs, wsrc;                                // RESIZED: the pictures are [3,hs,wsrc], sampled at scale ry = hs / h, rx = wsrc / w
-	double ry, rx;
-};
-
 // RESIZED (level 0 only): the staged value at (y, x) of the h x w grid is the bilinear sample (upsample_bilinear2d,
 // align_corners=False: hvs_lerp) of the [3,hs,wsrc] picture, R, G and B interpolated first (in double, kept in fp32) and the
 // colour converted afterwards, as a script that resizes and then calls the loss does. Reflection acts on (y, x). The plain
@@ -374,18 +306,6 @@ __global__ void __launch_bounds__(1024) k_hvs_finish(int n, const float *__restr
 // ---------------------------------------------------------------- backward
 struct HvsUpArgs { int h, w, ph, pw, nmc, mse, G; double sy, sx; float wgt; const float *wsi, *wst; long long pool; float *gpool; };
 
-// d loss / d (mean, mean-square) at one full-resolution pixel of one map
-__device__ __forceinline__ void hvs_pix_grad(const HvsStat &A, const HvsStat &B, int mse, float wgt, float &dmean, float &dmsq)
-{
-	dmean = wgt * hvs_dabs(A.mean - B.mean, mse);
-	dmsq = 0.0f;
-	if (!(A.var < HVS_VAR_FLOOR))
-	{
-		dmsq = (float)((double)(wgt * hvs_dabs(A.std - B.std, mse)) / (2.0 * A.std));
-		dmean = (float)((double)dmean - 2.0 * A.mean * (double)dmsq);
-	}
-}
-
 __global__ void __launch_bounds__(256) k_hvs_bwd_up(HvsUpArgs a)
 {
 	const int G = a.G, lane = threadIdx.x & (G - 1);
@@ -426,13 +346,14 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_up(HvsUpArgs a)
 	if (valid && lane == 0) { a.gpool[cell] = gm; a.gpool[ncell + cell] = gq; }
 }
 
-struct HvsGArgs { int h, w, ph, pw, nmc, mse, identity; float wgt; const float *wsi, *wst; long long maps; const float *gpool; };
-
 // d loss / d map[mc](y, x): the adjoint of the adaptive windows (a gather over the cells whose window holds the pixel), or the
-// direct comparison's derivative on an identity level; 0 outside the map
+// direct comparison's derivative on an identity level; 0 outside the map. FOV (the foveated loss, csrc/hvs_fov.hip): the map's
+// finished gradient, read from the workspace [nmc,h,w]. The plain instantiation is the function as it was.
+template <bool FOV>
 __device__ __forceinline__ float hvs_g_at(const HvsGArgs &a, int mc, int y, int x)
 {
 	if (y < 0 || y >= a.h || x < 0 || x >= a.w) return 0.0f;
+	if (FOV) return a.gpool[(size_t)mc * a.h * a.w + (size_t)y * a.w + x];
 	const size_t o = a.maps + (size_t)mc * a.h * a.w + (size_t)y * a.w + x;
 	const float xv = a.wsi[o];
 	if (a.identity) return a.wgt * hvs_dabs((double)xv - (double)a.wst[o], a.mse);
@@ -492,15 +413,7 @@ __device__ __forceinline__ float hvs_convT(const float (*G)[HVS_LP + 1], const f
 	return acc;
 }
 
-struct HvsBwdLevelArgs
-{
-	HvsGArgs g;
-	int nb, m0, last, pad;
-	float wres;
-	const float *filt, *glow_next, *low_i, *low_t;
-	float *glow;
-};
-
+template <bool FOV>
 __global__ void __launch_bounds__(256) k_hvs_bwd_level(HvsBwdLevelArgs a)
 {
 	__shared__ float G[HVS_LP][HVS_LP + 1], F[(2 + HVS_MAXB) * 25];
@@ -516,7 +429,7 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_level(HvsBwdLevelArgs a)
 		for (int i = tid; i < HVS_LP * HVS_LP; i += 256)
 		{
 			const int r = i / HVS_LP, c = i - r * HVS_LP;
-			G[r][c] = hvs_g_at(a.g, (a.m0 + b) * 3 + ch, by + r - 2, bx + c - 2);
+			G[r][c] = hvs_g_at<FOV>(a.g, (a.m0 + b) * 3 + ch, by + r - 2, bx + c - 2);
 		}
 		__syncthreads();
 		if (in) acc += hvs_convT(G, F + 50 + b * 25, ty, tx, qy, qx, h, w, by, bx);
@@ -530,8 +443,7 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_level(HvsBwdLevelArgs a)
 	}
 }
 
-struct HvsBwdImageArgs { HvsGArgs g; int rgb, pad; const float *filt, *glow0, *gscale; float *dimg; };
-
+template <bool FOV>
 __global__ void __launch_bounds__(256) k_hvs_bwd_image(HvsBwdImageArgs a)
 {
 	__shared__ float G[HVS_LP][HVS_LP + 1], F[50];
@@ -557,7 +469,7 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_image(HvsBwdImageArgs a)
 		for (int i = tid; i < HVS_LP * HVS_LP; i += 256)
 		{
 			const int r = i / HVS_LP, c = i - r * HVS_LP;
-			G[r][c] = hvs_g_at(a.g, ch, by + r - 2, bx + c - 2);
+			G[r][c] = hvs_g_at<FOV>(a.g, ch, by + r - 2, bx + c - 2);
 		}
 		__syncthreads();
 		if (in) t += hvs_convT(G, F + 25, ty, tx, qy, qx, h, w, by, bx);
@@ -579,8 +491,6 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_image(HvsBwdImageArgs a)
 		a.dimg[o] = s * gc[0]; a.dimg[plane + o] = s * gc[1]; a.dimg[2 * plane + o] = s * gc[2];
 	}
 }
-
-struct HvsBwdResizeArgs { int h, w, hs, wsrc; double ry, rx; const float *g, *gscale; float *dimg; };
 
 // The adjoint of the resized load: dL/d(source) [3,hs,wsrc] from dL/d(resized) g [3,h,w] (k_hvs_bwd_image's output, written
 // WITHOUT the upstream scalar, which multiplies each finished sum here: one rounding per element, so that an upstream gradient
@@ -621,7 +531,7 @@ __global__ void __launch_bounds__(256) k_hvs_bwd_resize(HvsBwdResizeArgs a)
 }
 
 // a resize of [3,Hs,Ws] to H x W the kernels take: no shrinking on either axis (no script does it; it would need another filter)
-static int hvs_resize_check(int Hs, int Ws, int H, int W)
+int hvs_resize_check(int Hs, int Ws, int H, int W)
 {
 	if (Hs <= 0 || Ws <= 0) { set_error("hvs: source size %dx%d is not positive", Hs, Ws); return FR_ERR_INVALID; }
 	if (H < Hs || W < Ws) { set_error("hvs: shrinking %dx%d to %dx%d is unsupported (the resize size must be at least the source size)", Hs, Ws, H, W); return FR_ERR_INVALID; }
@@ -629,6 +539,40 @@ static int hvs_resize_check(int Hs, int Ws, int H, int W)
 }
 
 static int hvs_group(long long window_elems) { return window_elems <= 16 ? 1 : (window_elems <= 256 ? 8 : 64); }
+
+// ---------------------------------------------------------------- the launchers csrc/hvs_fov.hip uses (hvs_common.h)
+void hvs_launch_level(bool resized, dim3 grid, hipStream_t stream, const HvsLevelArgs &a)
+{
+	if (resized) hipLaunchKernelGGL(k_hvs_level<true>, grid, dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL(k_hvs_level<false>, grid, dim3(256), 0, stream, a);
+}
+
+void hvs_launch_bwd_level(bool fov, dim3 grid, hipStream_t stream, const HvsBwdLevelArgs &a)
+{
+	if (fov) hipLaunchKernelGGL(k_hvs_bwd_level<true>, grid, dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL(k_hvs_bwd_level<false>, grid, dim3(256), 0, stream, a);
+}
+
+void hvs_launch_bwd_image(bool fov, dim3 grid, hipStream_t stream, const HvsBwdImageArgs &a)
+{
+	if (fov) hipLaunchKernelGGL(k_hvs_bwd_image<true>, grid, dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL(k_hvs_bwd_image<false>, grid, dim3(256), 0, stream, a);
+}
+
+void hvs_launch_bwd_resize(hipStream_t stream, const HvsBwdResizeArgs &a)
+{
+	hipLaunchKernelGGL(k_hvs_bwd_resize, dim3((a.wsrc + 63) / 64, (a.hs + 3) / 4), dim3(256), 0, stream, a);
+}
+
+void hvs_launch_cmp_direct(hipStream_t stream, const float *x, const float *y, long long n, int mse, float wgt, float *partials)
+{
+	hipLaunchKernelGGL(k_hvs_cmp_direct, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, x, y, n, mse, wgt, partials);
+}
+
+void hvs_launch_finish(hipStream_t stream, int n, const float *partials, float *out)
+{
+	hipLaunchKernelGGL(k_hvs_finish, dim3(1), dim3(1024), 0, stream, n, partials, out);
+}
 
 } // namespace fr
 
@@ -752,14 +696,14 @@ static int hvs_backward(int Hs, int Ws, int32_t H, int32_t W, double pooling_siz
 		a.wres = wstat / (float)(3ll * p.lh * p.lw);
 		a.filt = filters; a.glow_next = a.last ? nullptr : workspace + p.lv[l + 1].glow;
 		a.low_i = state_img + last; a.low_t = state_target + last; a.glow = workspace + v.glow;
-		hipLaunchKernelGGL(k_hvs_bwd_level, dim3((v.w + HVS_T - 1) / HVS_T, (v.h + HVS_T - 1) / HVS_T, 3), dim3(256), 0, stream, a);
+		hipLaunchKernelGGL(k_hvs_bwd_level<false>, dim3((v.w + HVS_T - 1) / HVS_T, (v.h + HVS_T - 1) / HVS_T, 3), dim3(256), 0, stream, a);
 		if (l == 0) g0 = a.g;
 	}
 	HvsBwdImageArgs b = {};
 	b.g = g0; b.rgb = rgb; b.filt = filters; b.glow0 = workspace + p.lv[0].glow;
 	b.gscale = Hs ? nullptr : grad_scale; // (resized: k_hvs_bwd_resize applies it)
 	b.dimg = Hs ? workspace + p.bwd_floats : dL_dimg;
-	hipLaunchKernelGGL(k_hvs_bwd_image, dim3((W + HVS_T - 1) / HVS_T, (H + HVS_T - 1) / HVS_T, 1), dim3(256), 0, stream, b);
+	hipLaunchKernelGGL(k_hvs_bwd_image<false>, dim3((W + HVS_T - 1) / HVS_T, (H + HVS_T - 1) / HVS_T, 1), dim3(256), 0, stream, b);
 	if (Hs)
 	{
 		HvsBwdResizeArgs r;

@@ -35,6 +35,9 @@ Target state: the target's pyramid statistics are kept from call to call and reu
 they were computed from -- the same tensor object (held by a weak reference), address, shape, strides and autograd _version,
 the same settings (the resize size among them), colour space and device (rasterizer.py's rule for "unchanged"). Anything else recomputes them in the same
 launches as the image's. There is no host synchronisation in the call.
+
+``MetamericLoss`` (metameric_loss.py, csrc/hvs_fov.hip) is the gaze-dependent loss of the same package: its docstring says what
+it supports.
 """
 import importlib
 import math
@@ -44,7 +47,7 @@ import torch
 
 from . import _native_hvs as _hvs
 
-__all__ = ["MetamericLossUniform", "pyramid_size"]
+__all__ = ["MetamericLossUniform", "MetamericLoss", "pyramid_size"]
 
 
 def pyramid_size(height, width, n_pyramid_levels):
@@ -198,3 +201,6 @@ class MetamericLossUniform:
         except BaseException:
             self._target = None  # (the state may not have been filled)
             raise
+
+
+from .metameric_loss import MetamericLoss  # noqa: E402  (it uses pack_filters and _resize_size from above)

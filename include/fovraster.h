@@ -432,6 +432,37 @@ int fr_hvs_backward_resized(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double
 	float *dL_dimg, void *stream);
 int64_t fr_hvs_resized_backward_floats(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double pooling_size, int32_t n_levels, int32_t n_orientations);
 
+/* The foveated (gaze-dependent) metameric loss, fused (csrc/hvs_fov.hip): MetamericLoss with use_bilinear_downup=True,
+ * use_l2_foveal_loss=False, use_radial_weight=False, use_fullres_l0=False, equi=False and the cropped 5x5 filters, the "HVS FOV"
+ * figure of hvs_loss_calc.py:21-75. The uniform loss above with another blur: every pixel of a band level has its own level of
+ * detail lod = max(0, log2(1e-6 + pooling size in pixels)) from the gaze, the level's own size and alpha, real_image_width,
+ * real_viewing_distance and mode (1 = "quadratic", 0 = "linear"), and the blur blends levels floor(lod) and floor(lod) + 1 of
+ * the band's mip chain (successively area-halved copies, each bilinearly sampled at the pixel; the last level, always 1x1, is
+ * a constant and also serves every lod beyond it). Restated from
+ *   metamer/odak_perception/foveation.py:6-179, radially_varying_blur.py:23-140, metameric_loss.py:86-191, :204-271.
+ * gaze_x, gaze_y: normalised image coordinates, x first; they may lie outside [0, 1].
+ * Hs, Ws: 0, 0 = img / target are [3,H,W]; else they are [3,Hs,Ws] and are resized to H x W in the level-0 load, as in
+ *   fr_hvs_forward_resized (Hs <= H, Ws <= W). H and W are multiples of 2^n_levels, and every band level's chain must end at
+ *   1x1 or 1x2: any other size is FR_ERR_INVALID (fr_last_error names the level and its size; the reference itself fails there).
+ * fr_hvs_fov_workspace_floats(.., which): floats of 0 = one picture's forward state (bands, both mip chains, lowpasses),
+ *   1 = the backward workspace, 2 = the partial sums, 3 = the LOD maps (doubles: two floats each; 8-byte aligned; behind the
+ *   maps, every level's largest value, from which the backward pass knows the chain levels that no pixel blends);
+ *   -1 for bad arguments.
+ * forward:  as fr_hvs_forward. lod: the LOD maps of every band level; lod_valid != 0 = it holds the maps of exactly these H, W,
+ *   n_levels, alpha, real_image_width, real_viewing_distance, mode and gaze from an earlier call and is not rebuilt, else the
+ *   call fills it (kernels on `stream`; a gaze change costs no host synchronisation).
+ * backward: as fr_hvs_backward / fr_hvs_backward_resized, from the two states and the LOD maps of the forward. Every sum is a
+ *   gather in a fixed order, with no atomics and no zero fill: the same bits on every run.
+ * The number of launches depends on H, W and n_levels only. */
+int64_t fr_hvs_fov_workspace_floats(int32_t Hs, int32_t Ws, int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t which);
+int fr_hvs_fov_forward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double alpha, double real_image_width, double real_viewing_distance,
+	int32_t mode, double gaze_x, double gaze_y, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb, const float *filters,
+	const float *img, const float *target, float *state_img, float *state_target, float *lod, int32_t lod_valid, float *partials, float *out,
+	void *stream);
+int fr_hvs_fov_backward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double alpha, double real_image_width, double real_viewing_distance,
+	int32_t mode, double gaze_x, double gaze_y, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb, const float *filters,
+	const float *state_img, const float *state_target, const float *lod, float *workspace, const float *grad_scale, float *dL_dimg, void *stream);
+
 /* Mean squared distance of every point to its three nearest neighbours: simple-knn's distCUDA2, the initial scale of
  * GaussianModel.create_from_pcd (replaces SimpleKNN::knn, fov3dgs/submodules/simple-knn/simple_knn.cu:185-220, as called by
  * distCUDA2, spatial.cu:15-25). points: [P,3] fp32 device array; mean_dist2: [P] fp32, written in full:

@@ -17,10 +17,17 @@ keyword left to the caller against the resize inside the kernels, the same proto
   per form torch.cuda.max_memory_allocated of one step above what was allocated before it, and whether the image gradient of
   two identical rounds is the same bits (torch lists upsample_bilinear2d_backward as non-deterministic; ours is a gather).
   fused_resize_not_slower_beyond_spread: fused_resize's p10 does not lie above interpolate_then_fused's p90.
+--foveated measures the gaze-dependent loss instead (fov3dgs_amd.odak_perception.MetamericLoss, csrc/hvs_fov.hip) and writes
+profiles/hvs_fov_bench.json: HVSLoss's defaults (alpha 0.05, width 1.0, distance 0.5, 5 levels, 6 orientations, MSE), at 1088x1920
+and from 1080x1920 pictures with the resize (resize="pyramid" against F.interpolate in front of the torch form), gaze at the
+centre and at (0.1, 0.1); loss + backward and the forward alone; three candidates alternating call by call, a new target tensor
+every round: fused_fov, torch_fov (tests/hvs_fov_ref.py in float32 on the GPU with its LOD maps built once, as the reference
+caches them) and fused_uniform_p9 (the uniform loss at pooling 9, MSE). Per candidate the peak memory of one step, and the
+relative difference of the two foveated losses. fused_faster_beyond_spread: fused_fov's p90 lies below torch_fov's p10.
 The filter coefficients come from tests/golden/ref_hvs.npz. No GPU, no run: there is no fallback.
 
 usage: python tools/hvs_bench.py [--steps 50] [--warmup 10] [--step-rounds 30] [--P 6000000] [--skip-step] [--resized-only]
-                                 [--out profiles/hvs_bench.json]
+                                 [--foveated] [--out profiles/hvs_bench.json]
 --resized-only measures the section "resized" alone and keeps the other sections of an existing --out file as they are."""
 import argparse
 import json
@@ -40,8 +47,8 @@ import fov3dgs_amd  # noqa: E402,F401
 from fov3dgs_amd import optim  # noqa: E402
 from fov3dgs_amd import synthetic as syn  # noqa: E402
 from fov3dgs_amd.gaussian_renderer import render  # noqa: E402
-from fov3dgs_amd.odak_perception import MetamericLossUniform, _native_hvs  # noqa: E402
-from tests import hvs_ref  # noqa: E402
+from fov3dgs_amd.odak_perception import MetamericLoss, MetamericLossUniform, _native_hvs, _native_hvs_fov  # noqa: E402
+from tests import hvs_fov_ref, hvs_ref  # noqa: E402
 
 ARGS = SimpleNamespace(position_lr_init=0.00016, feature_lr=0.0025, opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001)
 W, H = 1920, 1080
@@ -257,6 +264,94 @@ def resized(dev, a):
     return r
 
 
+FOV = dict(alpha=0.05, real_image_width=1.0, real_viewing_distance=0.5, mode="quadratic")  # hvs_loss_calc.py:22-23, :40
+
+
+def foveated_forms(dev, gaze, source):
+    """(name, fn(image [1,3,h,w], target) -> loss) for pictures of size `source`, (HL, WL) or (H, W) with the resize"""
+    f = filters()
+    resize = None if source == (HL, WL) else "pyramid"
+    fov = MetamericLoss(device=dev, n_pyramid_levels=LEVELS, n_orientations=ORIENTATIONS, use_l2_foveal_loss=False, loss_type="MSE",
+                        use_bilinear_downup=True, filters=f, **FOV)
+    uni = MetamericLossUniform(device=dev, pooling_size=9, n_pyramid_levels=LEVELS, n_orientations=ORIENTATIONS, loss_type="MSE",
+                               bilinear_downsampling=True, filters=f)
+    f32 = hvs_ref.filters_to(f, dtype=torch.float32, device=dev)
+    lods = hvs_fov_ref.lod_maps(gaze, HL, WL, LEVELS, FOV["alpha"], FOV["real_image_width"], FOV["real_viewing_distance"], FOV["mode"],
+                                torch.float32, dev)
+
+    def torch_fov(x, t):
+        if resize:
+            x = F.interpolate(x, size=(HL, WL), mode="bilinear", align_corners=False)
+            t = F.interpolate(t, size=(HL, WL), mode="bilinear", align_corners=False)
+        return hvs_fov_ref.fov_loss(x, t, f32, n_pyramid_levels=LEVELS, loss_type="MSE", lods=lods)
+
+    return (("fused_fov", lambda x, t: fov(x, t, gaze=gaze, resize=resize)), ("torch_fov", torch_fov),
+            ("fused_uniform_p9", lambda x, t: uni(x, t, resize=resize)))
+
+
+def foveated_one(dev, a, gaze, source):
+    gen = torch.Generator(device=dev).manual_seed(5)
+    base = torch.rand(1, 3, *source, device=dev, generator=gen)
+    image = (base + 0.05 * torch.randn(1, 3, *source, device=dev, generator=gen)).clamp(0, 1)
+    forms = foveated_forms(dev, gaze, source)
+
+    def step(fn, target, backward):
+        if not backward:
+            with torch.no_grad():
+                return fn(image, target), None
+        x = image.clone().requires_grad_(True)
+        loss = fn(x, target)
+        loss.backward()
+        return loss.detach(), x.grad
+
+    r = {}
+    for what, backward in (("loss_and_backward", True), ("forward_only", False)):
+        ms, values, grads = {k: [] for k, _ in forms}, {}, {k: [] for k, _ in forms}
+        for it in range(a.warmup + a.steps):
+            evs = []
+            target = base.clone()  # a new tensor every round: nothing of the target is reused from call to call
+            for k, fn in forms:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                loss, grad = step(fn, target, backward)
+                e1.record()
+                evs.append((k, e0, e1))
+                values[k] = loss
+                if backward and it < 2:
+                    grads[k].append(grad.clone())
+            torch.cuda.synchronize()
+            if it >= a.warmup:
+                for k, e0, e1 in evs:
+                    ms[k].append(e0.elapsed_time(e1))
+        q = {k: summary(v) for k, v in ms.items()}
+        q["loss"] = {k: float(v) for k, v in values.items()}
+        q["fov_loss_relative_difference_fused_vs_torch"] = abs(q["loss"]["fused_fov"] - q["loss"]["torch_fov"]) / q["loss"]["torch_fov"]
+        if backward:
+            q["image_gradient_of_two_identical_rounds_equal"] = {k: bool(torch.equal(*g)) for k, g in grads.items()}
+            q["fov_gradient_relative_l2_fused_vs_torch"] = float((grads["fused_fov"][0] - grads["torch_fov"][0]).norm() / grads["torch_fov"][0].norm())
+        del grads
+        q["peak_bytes_of_one_step"] = {k: peak_bytes(lambda fn=fn: step(fn, base.clone(), backward)) for k, fn in forms}
+        q["fused_faster_beyond_spread"] = bool(q["fused_fov"]["p90_ms"] < q["torch_fov"]["p10_ms"])
+        r[what] = q
+        torch.cuda.empty_cache()
+    return r
+
+
+def foveated(dev, a):
+    st = _native_hvs_fov.Settings(HL, WL, FOV["alpha"], FOV["real_image_width"], FOV["real_viewing_distance"], 1, 0.5, 0.5, LEVELS, ORIENTATIONS, 1, 1)
+    result = {"device": torch.cuda.get_device_name(0), "size": [HL, WL], "resized_from": [H, W], "levels": LEVELS, "orientations": ORIENTATIONS,
+              "loss_type": "MSE", "settings": FOV, "steps": a.steps, "warmup": a.warmup,
+              "torch_form": "tests/hvs_fov_ref.py, float32, grouped convolutions, LOD maps built once, no host synchronisation",
+              "state_bytes_per_picture": 4 * _native_hvs_fov.floats(st, 0), "backward_workspace_bytes": 4 * _native_hvs_fov.floats(st, 1),
+              "lod_bytes": 4 * _native_hvs_fov.floats(st, 3), "runs": {}}
+    for source in ((HL, WL), (H, W)):
+        for gaze in ([0.5, 0.5], [0.1, 0.1]):
+            name = f"{source[0]}x{source[1]}{'' if source == (HL, WL) else '_resized'}/gaze_{gaze[0]}_{gaze[1]}"
+            result["runs"][name] = foveated_one(dev, a, gaze, source)
+            print(json.dumps({name: result["runs"][name]}), flush=True)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -265,10 +360,18 @@ def main():
     ap.add_argument("--P", type=int, default=6_000_000)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--resized-only", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hvs_bench.json"))
+    ap.add_argument("--foveated", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "hvs_fov_bench.json" if a.foveated else "hvs_bench.json")
     assert torch.cuda.is_available(), "hvs_bench needs the MI355X"
     dev = "cuda:0"
+    if a.foveated:
+        result = foveated(dev, a)
+        with open(a.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+        return
     if a.resized_only:
         with open(a.out) as fh:
             result = json.load(fh)
