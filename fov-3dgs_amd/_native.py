@@ -156,7 +156,9 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov",
            "fr_hvs_workspace_floats", "fr_hvs_forward", "fr_hvs_backward",
            "fr_hvs_forward_resized", "fr_hvs_backward_resized", "fr_hvs_resized_backward_floats",
-           "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward")
+           "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward",
+           "fr_quality_blocks", "fr_quality_forward", "fr_quality_finish",
+           "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -309,6 +311,20 @@ def load():
     lib.fr_densify_plan.restype = C.c_int
     lib.fr_densify_rows.argtypes = [C.POINTER(DensifyRowsArgs), C.c_void_p]
     lib.fr_densify_rows.restype = C.c_int
+    lib.fr_quality_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.fr_quality_blocks.restype = C.c_int64
+    lib.fr_quality_forward.argtypes = [C.c_int32] * 4 + [_FP, _FP, _FP, C.c_void_p]
+    lib.fr_quality_forward.restype = C.c_int
+    lib.fr_quality_finish.argtypes = [C.c_int32] * 4 + [_FP, _FP, C.c_int32, C.c_int32, _FP, C.c_void_p]
+    lib.fr_quality_finish.restype = C.c_int
+    lib.fr_scale_decay_blocks.argtypes = [C.c_int32]
+    lib.fr_scale_decay_blocks.restype = C.c_int64
+    lib.fr_scale_decay_forward.argtypes = [C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_scale_decay_forward.restype = C.c_int
+    lib.fr_scale_decay_backward.argtypes = [C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_scale_decay_backward.restype = C.c_int
+    lib.fr_opacity_cap.argtypes = [C.c_int32, _FP, C.c_float, C.c_float, _FP, _FP, _FP, C.c_void_p]
+    lib.fr_opacity_cap.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -13,11 +13,16 @@ The choice inside a run of equal metrics -- most metrics are exactly 0 -- is arb
 here the rows are ordered by (metric, index) as torch.sort(stable=True) orders them, so the lowest indices of a tied run go
 first and the result is one bit pattern, run after run.
 
+Two more steps of prune.py's loop live here (csrc/prune_step.hip): ``scale_decay_loss`` (prune.py:257-261) and the opacity cap
+``reset_opacity_max`` / ``reset_opacity`` / ``reset_opacity_upper_bound`` (gaussian_model.py:421-431, :447-452). Its quality gate is
+fov3dgs_amd.quality.
+
 GPU tensors only: there is no CPU fallback. Everything runs on torch.cuda.current_stream() of the tensors' device. The
 scratch memory is one grow-only tensor per device (use it from one stream at a time). Transient memory of a prune: the
 outputs are allocated before the inputs are released, so for a moment the parameters and both moments exist twice (about
 4.3 GB at 6 M Gaussians)."""
 import ctypes as C
+import math
 
 import torch
 
@@ -281,3 +286,128 @@ def metric_pruning(model, cameras, pipe, bg, prune_ratio=0.1, metric="max_comp_e
     k = int(P * prune_ratio)
     prune_points(model, lowest_k_mask(metrics, k), n_pruned=k)
     return model
+
+
+# ---- the other steps of prune.py's loop (csrc/prune_step.hip) ------------------------------------------------------------
+class _ScaleDecay(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scaling, counts, threshold, raw):
+        lib = _native.load()
+        s = scaling.detach()
+        if not s.is_contiguous():
+            s = s.contiguous()
+        P, dev = s.shape[0], s.device
+        partials = torch.empty(int(lib.fr_scale_decay_blocks(P)), dtype=torch.float64, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.fr_scale_decay_forward(P, s.data_ptr(), counts.data_ptr(), threshold, int(raw), partials.data_ptr(), out.data_ptr(),
+                                            _stream(dev))
+        _check(rc, "scale_decay_forward")
+        ctx.save_for_backward(s, counts)
+        ctx.threshold, ctx.raw = threshold, raw
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        s, counts = ctx.saved_tensors
+        lib = _native.load()
+        P, dev = s.shape[0], s.device
+        g = g.detach().reshape(-1)[:1].to(device=dev, dtype=torch.float32).contiguous()  # read by the kernel: no host round trip
+        grad = torch.empty_like(s)
+        with torch.cuda.device(dev):
+            rc = lib.fr_scale_decay_backward(P, s.data_ptr(), counts.data_ptr(), ctx.threshold, int(ctx.raw), g.data_ptr(), grad.data_ptr(),
+                                             _stream(dev))
+        _check(rc, "scale_decay_backward")
+        return grad, None, None, None
+
+
+def scale_decay_loss(scaling, gs_count, threshold=4, raw=False):
+    """The scale-decay term of prune.py:257-261, ``(max(scaling, dim=1) * (gs_count - 4) * (gs_count > 4)).mean()``, as one
+    forward launch plus a one-workgroup finish and one backward launch instead of about eight elementwise / reduce kernels and
+    their autograd graph: mean_p( max_j s[p,j] * max(gs_count[p] - threshold, 0) ), a device scalar.
+
+    scaling: float32 [P,3] -- activated, as get_scaling returns it, or with raw=True the log-scales (``_scaling``; the exp is taken
+    in the kernel). gs_count: int32 [P] or [P,1], as render_pkg["gs_count"]; it receives no gradient. The gradient is dense
+    [P,3]: (count - threshold)+ / P in the column of the row's maximum (the lowest column among equals, torch.max's index), times
+    exp(raw) there with raw=True, 0 elsewhere, times the upstream gradient, which the kernel reads on the device: ``loss +=
+    scale_loss * scale_weight`` synchronises nothing. A row with count <= threshold adds exactly 0 and gets exactly 0, whatever
+    its scale. Sums are double, in a fixed order: the same bits on every run."""
+    for t in (scaling, gs_count):
+        if not torch.is_tensor(t):
+            raise TypeError(f"fovraster scale_decay_loss expects torch tensors, got {type(t).__name__}")
+    if scaling.dim() != 2 or scaling.shape[1] != 3 or scaling.shape[0] == 0:
+        raise ValueError(f"scaling: expected [P,3] with P > 0, got {list(scaling.shape)}")
+    if scaling.dtype != torch.float32:
+        raise ValueError(f"scaling must be float32, got {scaling.dtype}")
+    P = scaling.shape[0]
+    counts = _flat(gs_count, P, "gs_count")
+    if counts.dtype != torch.int32:
+        raise ValueError(f"gs_count must be the rasterizer's int32 counts, got {counts.dtype}")
+    if isinstance(threshold, bool) or not isinstance(threshold, int) or not -2 ** 31 <= threshold < 2 ** 31:
+        raise ValueError(f"threshold must be an int32 value, got {threshold!r}")
+    _require_gpu("scale_decay_loss", scaling, counts)
+    return _ScaleDecay.apply(scaling, counts.detach().contiguous(), threshold, bool(raw))
+
+
+@torch.no_grad()
+def _cap_opacity(model, cap, what):
+    if isinstance(cap, bool) or not isinstance(cap, (int, float)) or not 0.0 < float(cap) < 1.0:
+        raise ValueError(f"{what}: the cap must lie inside (0, 1), got {cap!r}")
+    cap = float(cap)
+    opt = model.optimizer
+    groups = [g for g in opt.param_groups if g.get("name") == "opacity"]
+    if len(groups) != 1:
+        raise ValueError(f"{what}: the optimizer has {len(groups)} groups named 'opacity'")
+    group = groups[0]
+    old = group["params"][0]
+    if old is not model._opacity:
+        raise ValueError(f"{what}: the 'opacity' group's parameter is not model._opacity")
+    if old.dim() not in (1, 2) or (old.dim() == 2 and old.shape[1] != 1):
+        raise ValueError(f"{what}: _opacity must be [P,1] or [P], got {list(old.shape)}")
+    if old.dtype != torch.float32:
+        raise ValueError(f"{what}: _opacity must be float32, got {old.dtype}")
+    _require_gpu(what, old)
+    raw = old.detach().contiguous()
+    P, dev = raw.shape[0], raw.device
+    st = opt.state.get(old, None)
+    new = torch.empty_like(raw)
+    m1, m2 = (torch.empty_like(raw), torch.empty_like(raw)) if st is not None else (None, None)
+    cap_logit = math.log(cap / (1.0 - cap))
+    lib = _native.load()
+    with torch.cuda.device(dev):
+        rc = lib.fr_opacity_cap(P, raw.data_ptr() or None, cap, cap_logit, new.data_ptr() or None,
+                                None if m1 is None else m1.data_ptr() or None, None if m2 is None else m2.data_ptr() or None, _stream(dev))
+    _check(rc, "opacity_cap")
+    # replace_tensor_to_optimizer (gaussian_model.py:609-622); a NEW tensor on purpose: the rasterizer's "unchanged inputs" and
+    # packed-layout caches key on the tensors' identity and version
+    param = torch.nn.Parameter(new.requires_grad_(True))
+    if st is not None:
+        st["exp_avg"], st["exp_avg_sq"] = m1, m2
+        del opt.state[old]
+        opt.state[param] = st
+    group["params"][0] = param
+    model._opacity = param
+    return param
+
+
+def reset_opacity_max(model, max=0.99):
+    """GaussianModel.reset_opacity_max (gaussian_model.py:427-431, with replace_tensor_to_optimizer :609-622): every opacity above
+    `max` becomes `max`. ONE launch reads ``model._opacity`` and writes the new raw opacities -- float32(logit(max)), evaluated
+    in double, where sigmoid(raw) > max -- and the zeroed exp_avg / exp_avg_sq; then a new nn.Parameter goes into the "opacity"
+    group, into optimizer.state (the same state dict: `step` and every other key stay; a group without state only gets its
+    parameter replaced) and onto the model. Works with torch.optim.Adam and fov3dgs_amd.optim.Adam; nothing synchronises.
+
+    A difference from the reference, on purpose: it passes EVERY row through logit(sigmoid(raw)), which moves the rows under the
+    cap by rounding noise (and sends raw values beyond +-17 to +-inf); here those rows keep their bits, and a NaN stays NaN.
+    Returns the new parameter."""
+    return _cap_opacity(model, max, "reset_opacity_max")
+
+
+def reset_opacity(model):
+    """GaussianModel.reset_opacity (gaussian_model.py:421-424): reset_opacity_max with the cap 0.01."""
+    return _cap_opacity(model, 0.01, "reset_opacity")
+
+
+def reset_opacity_upper_bound(model, upper_bound):
+    """GaussianModel.reset_opacity_upper_bound (gaussian_model.py:447-452): reset_opacity_max with the cap `upper_bound`."""
+    return _cap_opacity(model, upper_bound, "reset_opacity_upper_bound")

@@ -570,6 +570,54 @@ typedef struct fr_compact_args {
 int fr_compact_plan(int32_t P, const uint8_t *mask, int32_t invert, int32_t *count_out, void *workspace, void *stream);
 int fr_compact_rows(const fr_compact_args *args, void *stream);
 
+/* The quality gate of the pruning loop (csrc/quality.hip; replaces test_ssim_loss / test_psnr_loss, fov3dgs/prune.py:137-174 --
+ * two renders, the torch ssim and psnr and a host synchronisation per view -- and utils/image_utils.py:14-19 mse / psnr).
+ * img / target: [C,H,W] fp32 device tensors. Everything runs on `stream` with no host synchronisation, no allocation and no
+ * float atomics: every output is one bit pattern, run after run.
+ *   forward: partials[3 b .. 3 b + 2] = (sum ssim_map, sum (img - target)^2, sum |img - target|) over tile b (16 x 32 pixels of
+ *            one channel, channel-major), b < fr_quality_blocks(C,H,W) (0 for sizes the kernels do not take: C > 65535, ...).
+ *            The SSIM map is the one of fr_l1_ssim_forward (loss_utils.py:37-76: 11x11 window, sigma 1.5, zero padding);
+ *            with_ssim = 0 skips it and leaves the first sum 0. |img - target| and its tile sum are fp32, as in
+ *            fr_l1_ssim_forward; the squared error is evaluated and added in double from the fp32 inputs.
+ *   finish:  one workgroup. The C channels are `rows` consecutive groups of C / rows (rows = 1: the whole picture, what
+ *            prune.py measures; rows = C: one value per channel, what image_utils.psnr returns for a [3,H,W] input). For group
+ *            r, with n = (C / rows) H W and the sums added in double in tile order:
+ *              per_view[4 (slot + r) .. + 3] = (ssim = sum0 / n, psnr = 20 log10(1 / sqrt(mse)), l1 = sum2 / n, mse = sum1 / n)
+ *            psnr is evaluated in double and is +inf for mse = 0, as in the reference. per_view: float [capacity][4] owned by
+ *            the caller; slot + rows <= capacity. accum (optional, NULL = none): double[4] owned by the caller,
+ *            += (ssim, psnr, l1, 1) per group with the fp32 values above: the running sums over the views and the view count
+ *            (zero it to reset). partials and accum must be 8-byte aligned. */
+int64_t fr_quality_blocks(int32_t C, int32_t H, int32_t W);
+int fr_quality_forward(int32_t C, int32_t H, int32_t W, int32_t with_ssim, const float *img, const float *target, double *partials, void *stream);
+int fr_quality_finish(int32_t C, int32_t H, int32_t W, int32_t rows, const double *partials, float *per_view, int32_t slot, int32_t capacity,
+	double *accum, void *stream);
+
+/* The scale-decay loss of the pruning loop's training step (csrc/prune_step.hip; replaces prune.py:257-261 and its autograd):
+ *   loss = mean_p( max_j s[p][j] * max(counts[p] - threshold, 0) ),  s = scaling (raw = 0: activated, as get_scaling returns it)
+ *   or exp(scaling) (raw != 0: the log-scales, the exp is taken in the kernel). scaling: [P,3] fp32, counts: [P] int32 as the
+ *   rasterizer's gs_count. A row with counts <= threshold adds exactly 0 to the value and gets a gradient of exactly 0.
+ *   forward:  one launch that leaves a double per workgroup in partials[fr_scale_decay_blocks(P)] (8-byte aligned, owned by the
+ *             caller) and a one-workgroup finish: *out (a DEVICE float) = the sum in double, in workgroup order, divided by P.
+ *   backward: dL_dscaling [P,3], written in full: g (counts[p] - threshold)+ / P in the column of the row's maximum -- the
+ *             lowest column among equals, torch.max's index -- times exp(scaling) there when raw != 0; 0 elsewhere.
+ *             g = *grad_scale (a DEVICE scalar, the upstream gradient) or 1 when grad_scale is NULL.
+ * No host synchronisation, no allocation, no float atomics. P must be positive. */
+int64_t fr_scale_decay_blocks(int32_t P);
+int fr_scale_decay_forward(int32_t P, const float *scaling, const int32_t *counts, int32_t threshold, int32_t raw, double *partials, float *out,
+	void *stream);
+int fr_scale_decay_backward(int32_t P, const float *scaling, const int32_t *counts, int32_t threshold, int32_t raw, const float *grad_scale,
+	float *dL_dscaling, void *stream);
+
+/* The opacity cap after a pruning round (csrc/prune_step.hip; replaces the device work of reset_opacity / reset_opacity_max /
+ * reset_opacity_upper_bound, fov3dgs/scene/gaussian_model.py:421-431, :447-452, and the two zeros_like of
+ * replace_tensor_to_optimizer, :609-622), one launch:
+ *   out[i] = 1 / (1 + expf(-raw[i])) > max_opacity ? cap_logit : raw[i]      (the input's bits where it is not capped: a NaN
+ *   stays; the reference passes those rows through logit(sigmoid()), which moves them by rounding noise)
+ *   exp_avg[i] = exp_avg_sq[i] = 0                                            (either may be NULL: a group without state)
+ * cap_logit: the caller's log(max / (1 - max)). max_opacity must lie inside (0, 1). P = 0 launches nothing. */
+int fr_opacity_cap(int32_t P, const float *raw_opacity, float max_opacity, float cap_logit, float *out, float *exp_avg, float *exp_avg_sq,
+	void *stream);
+
 /* Densification: the steps of GaussianModel that add rows (fov3dgs/scene/gaussian_model.py:666-851, :865-867). Every decision
  * is taken per SOURCE row, so a whole densify_and_prune -- two torch.cat and two prune_points over the full training state in
  * the reference -- is one plan and one pass over the state. Everything runs on `stream` with no host synchronisation and no
