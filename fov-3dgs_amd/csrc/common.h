@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "../../include/fovraster.h"
 
 #define FR_TILE 16            // tile edge in pixels (reference config.h:15-17 BLOCK_X/BLOCK_Y)
@@ -18,6 +19,15 @@
 // them run at a time (2 waves/SIMD), the other finds the slab counters empty -- 384-thread workgroups (3 waves/SIMD)
 // measured no faster (0.253 vs 0.247 ms): the kernel follows its heaviest slabs, not its occupancy
 #define FR_BIN_BLOCKS 512
+// A frame that shares the GPU with other frames (fr_forward_args.no_helper_streams bit 1, frame_shares_gpu) runs its head kernels in
+// a geometry that leaves registers and LDS to the neighbouring frame's emission, sort and blend:
+#ifndef FR_PROJ_SHARED_NUM
+#define FR_PROJ_SHARED_NUM 3                   // k_project's grid then: this fraction of the device's CUs (a workgroup fills a CU: the others stay free)
+#define FR_PROJ_SHARED_DEN 4
+#endif
+#ifndef FR_BIN_SHARED_THREADS
+#define FR_BIN_SHARED_THREADS 512              // k_bin's workgroup then (k_emit keeps FR_EMIT_THREADS and replays k_bin's slabs: EmitArgs::bin_bw)
+#endif
 #define FR_PROJ_MAX_WAVES 8192                 // k_project's grid is capped to this many waves ...
 #define FR_CROW_PAD (64 * FR_PROJ_MAX_WAVES)     // ... each of which may leave its last chunk's worth of row slots unused
 #define FR_LDS_HIST_MAX_TILES 16384 // per-workgroup LDS tile histogram of 32-bit counts up to 64 KiB
@@ -444,6 +454,14 @@ __device__ __forceinline__ float4 act_rotation(float4 v, float *inv_norm = nullp
 	return make_float4(v.x / d, v.y / d, v.z / d, v.w / d);
 }
 
+// Does this frame share the GPU with other frames (fovraster.h: bit 1 of no_helper_streams)? FOVRASTER_LONE_GEOMETRY=1 (read once)
+// says no for every frame: A / B runs of the head kernels' two geometries under the same host code.
+inline bool frame_shares_gpu(const fr_forward_args *a)
+{
+	static const bool lone = []() { const char *e = getenv("FOVRASTER_LONE_GEOMETRY"); return e && e[0] == '1'; }();
+	return (a->no_helper_streams & FR_FRAME_SHARES_GPU) != 0 && !lone;
+}
+
 // stage launchers (implemented in the .hip files)
 struct FwdCtx {
 	fr_forward_args *a;
@@ -452,6 +470,7 @@ struct FwdCtx {
 	int fov_split;      // RF: the two level states of a two-level tile go to different waves (k_project clears those tiles' pixels)
 	uint8_t *visibility; // fr_forward_ext.visibility of the call, or null
 	int bin_wgs;        // workgroups k_bin ran with (k_emit replays the same number)
+	int bin_bw;         // ... and the waves of each (launch_bin: FR_BIN_THREADS / 64, or FR_BIN_SHARED_THREADS / 64): k_emit replays their slabs
 	int hist_mode;      // k_bin / k_emit: 0 = global tile counters, 1 = LDS histogram of 32-bit counts, 2 = of 16-bit counts (launch_bin decides)
 	int scan_fused;     // the tile scan ran as the tail of k_bin (launch_bin decides): no k_tile_scan launch
 	int heavy4, heavy2; // tiles with >= 2048 / 512..2047 instances (leading entries of tile_order)

@@ -1075,9 +1075,13 @@ __device__ __forceinline__ void colour_item(const PreArgs &a, const bool rows_ok
 #define BUMP_TILE(ti) do { if (LDSH == 2) atomicAdd(&lds_hist[(ti) >> 1], 1u << (16 * ((ti) & 1))); \
 	else if (LDSH) atomicAdd(&lds_hist[(ti)], 1u); else atomicAdd(&a.tile_count[(ti)], 1u); } while (0)
 static_assert((FR_BIN_THREADS / 64) * FR_HIST16_MAX_SLABS * 64 <= 65535, "a workgroup's items must fit a 16-bit tile count (LDSH == 2)");
-template <int VARIANT, int LDSH, bool PACKED = false, bool CROW = false>
-__global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
+// BT: the workgroup's threads (launch_bin: FR_BIN_THREADS; FR_BIN_SHARED_THREADS for a foveated frame that shares the GPU). The slabs a
+// workgroup takes follow from BT, and k_emit replays them (EmitArgs::bin_bw).
+template <int VARIANT, int LDSH, bool PACKED = false, bool CROW = false, int BT = FR_BIN_THREADS>
+__global__ void __launch_bounds__(BT) k_bin(const PreArgs a)
 {
+	static_assert(BT % 64 == 0 && BT >= FR_TILE_SCAN_THREADS && (LDSH != 2 || (BT / 64) * FR_HIST16_MAX_SLABS * 64 <= 65535),
+		"whole waves, enough of them for the fused tile scan, and (LDSH == 2) a workgroup's items within a 16-bit tile count");
 	static_assert(!(PACKED && CROW), "the packed model layout has its own rows");
 	constexpr bool CULL = VARIANT != FR_VARIANT_ORIGINAL;
 	constexpr bool FOV = is_fov(VARIANT);                            // level map + level filter
@@ -1102,15 +1106,15 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		// 1080p frame, and a 1440p frame's table fits beside its histogram. Sixteen loads at a time (written as a plain copy loop
 		// every iteration waited for its own load: a 10 us prologue on every CU before any work); eight lanes pack a word.
 		const float *gmin = a.tile_lv + a.T, *gbl = a.tile_lv + 4 * (size_t)a.T;
-		for (int t0 = threadIdx.x; t0 < a.T; t0 += 16 * FR_BIN_THREADS)
+		for (int t0 = threadIdx.x; t0 < a.T; t0 += 16 * BT)
 		{
 			float v[16], f[16];
 #pragma unroll
-			for (int k = 0; k < 16; k++) { const int t = min(t0 + k * FR_BIN_THREADS, a.T - 1); v[k] = gmin[t]; f[k] = gbl[t]; }
+			for (int k = 0; k < 16; k++) { const int t = min(t0 + k * BT, a.T - 1); v[k] = gmin[t]; f[k] = gbl[t]; }
 #pragma unroll
 			for (int k = 0; k < 16; k++)
 			{
-				const int t = t0 + k * FR_BIN_THREADS;
+				const int t = t0 + k * BT;
 				// (a NaN level -- a gaze far outside the frame with a steep alpha -- fails `tile_min < highest level + 1` for every Gaussian in the
 				// reference, RF rasterizer_impl.cu:802: coded as 7, which fails it for the highest levels 0..3 the table serves)
 				uint32_t nib = t < a.T ? ((v[k] == v[k] ? (uint32_t)min(max(f2i(v[k]), 0), 7) : 7u) | (f[k] != 0.0f ? 8u : 0u)) : 0u;
@@ -1121,7 +1125,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		}
 	}
 	if (LDSH)
-		for (int t = threadIdx.x; t < hist_words; t += FR_BIN_THREADS) lds_hist[t] = 0;
+		for (int t = threadIdx.x; t < hist_words; t += BT) lds_hist[t] = 0;
 	// "giant" splats (FR_GIANT_TNUM+ tiles, up to the whole frame = 128 wave steps) are set aside here and walked
 	// by ALL waves of the workgroup after the slab loop: left to the wave that met them they were the kernel's
 	// critical path
@@ -1151,23 +1155,23 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	// (dynamic LDS behind the histogram and the table, 16-byte aligned: the waves' staging rows / the pair loop's 64-byte row per
 	// lane (see there), and the owner rows of pair_owner_scan)
 	float4 *const s_orec = (float4 *)(lds_hist + ((hist_words + ((FOV && a.lds_tiles) ? tab_words : 0) + 3) & ~3));
-	int *const s_own = (int *)(s_orec + 4 * FR_BIN_THREADS);
+	int *const s_own = (int *)(s_orec + 4 * BT);
 	// [proj_waves + 1] first item of every cull-pass region: a copy in LDS, or -- when the histogram of a 4K tile grid leaves no room
 	// for its 32 KiB -- the table in global memory (the slab's binary search then costs thirteen L2 round trips)
 	// (two typed pointers, never one selected pointer: that one would be a generic address and every probe a flat load)
-	const uint32_t *const s_wbase = (const uint32_t *)(s_own + FR_BIN_THREADS);
+	const uint32_t *const s_wbase = (const uint32_t *)(s_own + BT);
 	const uint32_t *const g_wbase = a.geom.wbase;
 	if (a.wbase_lds)
 	{
-		uint32_t *const dst = (uint32_t *)(s_own + FR_BIN_THREADS);
+		uint32_t *const dst = (uint32_t *)(s_own + BT);
 		// (sixteen loads at a time, see the table fill above; visible after the workgroup barrier below)
-		for (int w0 = threadIdx.x; w0 <= a.proj_waves; w0 += 16 * FR_BIN_THREADS)
+		for (int w0 = threadIdx.x; w0 <= a.proj_waves; w0 += 16 * BT)
 		{
 			uint32_t v[16];
 #pragma unroll
-			for (int k = 0; k < 16; k++) v[k] = a.geom.wbase[min(w0 + k * FR_BIN_THREADS, a.proj_waves)];
+			for (int k = 0; k < 16; k++) v[k] = a.geom.wbase[min(w0 + k * BT, a.proj_waves)];
 #pragma unroll
-			for (int k = 0; k < 16; k++) if (w0 + k * FR_BIN_THREADS <= a.proj_waves) dst[w0 + k * FR_BIN_THREADS] = v[k];
+			for (int k = 0; k < 16; k++) if (w0 + k * BT <= a.proj_waves) dst[w0 + k * BT] = v[k];
 		}
 		__syncthreads();
 	}
@@ -1182,7 +1186,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	}
 	const int V = (int)a.geom.slab_ctr[1]; // entries of vis_list (the cull pass's last workgroup)
 	const int nslabs = (V + 63) / 64;
-	const int nwaves = (int)gridDim.x * (FR_BIN_THREADS / 64);
+	const int nwaves = (int)gridDim.x * (BT / 64);
 	const float *tile_min = FOV ? a.tile_lv + a.T : nullptr;
 	const float *tile_bl = FOV ? a.tile_lv + 4 * (size_t)a.T : nullptr;
 	// Wave-uniform walk of ONE splat's rectangle: lanes take tiles k0 + lane, k0 + lane + kstep, ... of the on
@@ -1247,7 +1251,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 	uint32_t q_ = 0;
 	if (lane == 0) q_ = atomicAdd(&s_next_slab, 1u);
 	q_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)q_);
-	constexpr int BW_ = FR_BIN_THREADS / 64;
+	constexpr int BW_ = BT / 64;
 	const int slab = (int)blockIdx.x * BW_ + (int)(q_ % BW_) + (int)(q_ / BW_) * nwaves; // (increasing in q)
 	if (slab >= nslabs) break;
 	const int nv = min(64, V - slab * 64);
@@ -1477,7 +1481,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		else rows_store<3>(r, orec, a.geom.rec + 3 * (size_t)slab * 64, nv, lane);
 	}
 	} // slab loop
-	// ---- giant splats: every wave of the workgroup takes every (FR_BIN_THREADS / 64)-th step ----
+	// ---- giant splats: every wave of the workgroup takes every (BT / 64)-th step ----
 	__syncthreads();
 	const int ng = min((int)s_ng, FR_GIANT_MAX);
 	for (int g = 0; g < ng; g++)
@@ -1488,7 +1492,7 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		const uint32_t xy = __float_as_uint(w2.z);
 		uint32_t cnt = 0, bits = 0;
 		walk_uniform((int)(xy & 0xffffu), (int)(xy >> 16), (int)__float_as_uint(w2.w), __float_as_uint(w3.x), ob, w3.y + 1,
-			(uint32_t)(threadIdx.x & ~63u), (uint32_t)FR_BIN_THREADS, cnt, bits);
+			(uint32_t)(threadIdx.x & ~63u), (uint32_t)BT, cnt, bits);
 		if (lane == 0) { atomicAdd(&s_gcount[g], cnt); if (FOV) atomicOr(&s_gmask[g], bits); }
 	}
 	__syncthreads();
@@ -1535,19 +1539,19 @@ __global__ void __launch_bounds__(FR_BIN_THREADS) k_bin(const PreArgs a)
 		// bucket is whatever order the atomics arrive in; the per-tile sort does not care.
 		__syncthreads();
 		uint32_t *out = a.hist + (size_t)blockIdx.x * a.T;
-		for (int t0 = threadIdx.x; t0 < a.T; t0 += 4 * FR_BIN_THREADS)
+		for (int t0 = threadIdx.x; t0 < a.T; t0 += 4 * BT)
 		{
 			uint32_t h[4], o[4];
 #pragma unroll
 			for (int k = 0; k < 4; k++)
 			{
-				const int t = t0 + k * FR_BIN_THREADS;
+				const int t = t0 + k * BT;
 				h[k] = t < a.T ? (LDSH == 2 ? (lds_hist[t >> 1] >> (16 * (t & 1))) & 0xffffu : lds_hist[t]) : 0u;
 			}
 #pragma unroll
-			for (int k = 0; k < 4; k++) o[k] = h[k] ? atomicAdd(&a.tile_count[t0 + k * FR_BIN_THREADS], h[k]) : 0u;
+			for (int k = 0; k < 4; k++) o[k] = h[k] ? atomicAdd(&a.tile_count[t0 + k * BT], h[k]) : 0u;
 #pragma unroll
-			for (int k = 0; k < 4; k++) { const int t = t0 + k * FR_BIN_THREADS; if (t < a.T && h[k]) out[t] = o[k]; }
+			for (int k = 0; k < 4; k++) { const int t = t0 + k * BT; if (t < a.T && h[k]) out[t] = o[k]; }
 		}
 		// The tile scan as the tail of this kernel (round 6; a kernel of its own it was 15 us + a 9-us launch gap of pure latency on
 		// the frame's critical path): the LAST workgroup to get here -- found with a counter, as in k_project -- has every
@@ -1587,6 +1591,7 @@ struct EmitArgs {
 	const uint32_t *totals; // ImageWS::totals: [0] = the frame's number of instances (k_tile_scan)
 	uint32_t capacity;      // instances `entries` has room for ...
 	uint32_t items_cap;     // ... and blend work items the frame's blend grid covers (see fr_forward)
+	int bin_bw;             // waves of k_bin's workgroups (FwdCtx::bin_bw): which slabs the workgroup of this number took
 };
 // LDSH: the workgroup's write cursor of every tile lives in LDS, initialised to
 // tile start + (instances of the same tile owned by lower-numbered workgroups).
@@ -1830,7 +1835,8 @@ __global__ void __launch_bounds__(FR_EMIT_THREADS) k_emit(const EmitArgs a)
 	}; // process(slab)
 	{
 		// the slabs k_bin's wave of the same number took (the bucket offsets are per workgroup): wave, wave + waves, ...
-		constexpr int BW = FR_BIN_THREADS / 64;
+		// (k_bin's workgroup may be smaller than this kernel's: a frame that shares the GPU, launch_bin)
+		const int BW = a.bin_bw;
 		const int bin_waves = (int)gridDim.x * BW;
 		// the workgroup's s-th slab: k_bin's wave (s mod BW) of this workgroup took it in its round s / BW
 		auto slab_of = [&](const int s) { return (int)blockIdx.x * BW + s % BW + (s / BW) * bin_waves; };
@@ -2039,6 +2045,7 @@ int launch_project(FwdCtx &c)
 		// persistent waves: exactly as many workgroups as the device keeps resident (a second, partial round of
 		// workgroups would run on a half-empty chip)
 		static thread_local int resident_of[8][6]; // per host thread and device (zero = not asked yet)
+		static thread_local int cus_of[8];         // ... and the device's CUs
 		int cur_dev = 0;
 		(void)hipGetDevice(&cur_dev);
 		int *const resident = resident_of[cur_dev & 7];
@@ -2057,9 +2064,17 @@ int launch_project(FwdCtx &c)
 				hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, FR_PROJ_THREADS, 0) != hipSuccess || per_cu < 1)
 			{ per_cu = 4; prop.multiProcessorCount = 256; }
 			resident[slot] = per_cu * prop.multiProcessorCount;
+			cus_of[cur_dev & 7] = prop.multiProcessorCount;
 		}
+		// A frame that shares the GPU with other frames (frame_shares_gpu) keeps fewer waves resident, so that the neighbouring frame's
+		// emission, sort and blend find whole CUs free beside this kernel: as many workgroups as FR_PROJ_SHARED_NUM / FR_PROJ_SHARED_DEN of
+		// the device's CUs. Every consumer of the grid takes it from proj_waves / proj_cpw: the last
+		// workgroup's scan, k_bin's copy of the running counts, the tile and visibility clears.
+		const bool shared = frame_shares_gpu(a);
+		int cap = resident[slot];
+		if (shared) { const int part = (int)((int64_t)cus_of[cur_dev & 7] * FR_PROJ_SHARED_NUM / FR_PROJ_SHARED_DEN); cap = part < cap ? (part > 0 ? part : 1) : cap; }
 		const int pchunks = (a->P + FR_PROJ_THREADS - 1) / FR_PROJ_THREADS;
-		const int pmax = resident[slot] < FR_PROJ_MAX_WAVES / (FR_PROJ_THREADS / 64) ? resident[slot] : FR_PROJ_MAX_WAVES / (FR_PROJ_THREADS / 64);
+		const int pmax = cap < FR_PROJ_MAX_WAVES / (FR_PROJ_THREADS / 64) ? cap : FR_PROJ_MAX_WAVES / (FR_PROJ_THREADS / 64);
 		const dim3 pgrid(pchunks < pmax ? pchunks : pmax), pblock(FR_PROJ_THREADS);
 		c.proj_waves = (int)pgrid.x * (FR_PROJ_THREADS / 64);
 		c.proj_cpw = proj_chunks_per_wave(a->P, c.proj_waves);
@@ -2083,7 +2098,6 @@ int launch_bin(FwdCtx &c)
 	const fr_forward_args *a = c.a;
 	PreArgs p = make_pre_args(c);
 	int nblk = bin_blocks(a->P);
-	const dim3 block(FR_BIN_THREADS);
 	// Where the tiles are counted: an LDS histogram per workgroup of 32-bit counts (grids up to 16 Ki tiles), of 16-bit counts
 	// (up to 34 816 tiles: a workgroup then takes fewer than 65 536 items, so the resident workgroups must cover all
 	// P Gaussians with a margin), or global counters.
@@ -2098,11 +2112,24 @@ int launch_bin(FwdCtx &c)
 	c.hist_mode = c.img.hist == nullptr ? 0 : (c.T <= FR_LDS_HIST_MAX_TILES ? 1 :
 		(wgs_lo * (FR_BIN_THREADS / 64) * (int64_t)(FR_HIST16_MAX_SLABS - 1) * 64 >= (int64_t)a->P ? 2 : 0)); // (wave w takes slabs w, w + waves, ...)
 	const bool ldsh = c.hist_mode != 0;
+	// the packed model layout and the candidate rows are compile-time variants of the kernel (run-time tests on the pointers cost
+	// the ordinary path 5 %): packed needs both packed tensors; the rows exist when k_project stored them (foveated variants,
+	// unpacked cull pass, scales + rotations given)
+	const bool packed = a->packed_geom && a->packed_colour;
+	const bool crow = !packed && is_fov(a->variant) && a->packed_cull == nullptr && a->cov3D_precomp == nullptr;
+	// A frame that shares the GPU with other frames bins with smaller workgroups -- still one per CU, on the same grid (k_emit replays
+	// it, and its scattered stores are priced per CU) -- so that a sort workgroup or blend waves of the neighbouring frame fit beside
+	// them. Instantiated for the shapes such frames have: foveated, four level rows, 32-bit LDS histogram,
+	// candidate rows or the packed model.
+	const bool shared = FR_BIN_SHARED_THREADS != FR_BIN_THREADS && frame_shares_gpu(a) && a->variant == FR_VARIANT_FOV_PCHECK_OBB &&
+		c.fov.levels <= FR_FOV_LEVELS && c.hist_mode == 1 && (packed || crow);
+	const int bt = shared ? FR_BIN_SHARED_THREADS : FR_BIN_THREADS;
+	const dim3 block(bt);
 	// LDS per workgroup: tile histogram (+ RF: the 4-bit tile table), the waves' staging / owner rows, the cull pass's running counts
 	p.lds_tiles = (is_fov(a->variant) && ldsh) ? 1 : 0;
 	const size_t hist_bytes = c.hist_mode == 2 ? (size_t)((c.T + 1) / 2) * sizeof(uint32_t) : (ldsh ? (size_t)c.T * sizeof(uint32_t) : 0);
 	const size_t lds_fixed = ((hist_bytes + (p.lds_tiles ? lds_tile_table_bytes(c.T) : 0) + 15) & ~(size_t)15) +
-		(size_t)FR_BIN_THREADS * (4 * sizeof(float4) + sizeof(int));
+		(size_t)bt * (4 * sizeof(float4) + sizeof(int));
 	const size_t wbase_bytes = (size_t)(c.proj_waves + 1) * sizeof(uint32_t);
 	p.wbase_lds = lds_fixed + wbase_bytes <= 156u * 1024u ? 1 : 0; // (a 4K grid's 16-bit histogram + a large cloud's 32 KiB of counts do not both fit)
 	size_t lds = lds_fixed + (p.wbase_lds ? wbase_bytes : 0);
@@ -2130,7 +2157,7 @@ int launch_bin(FwdCtx &c)
 			int per_cu = 0, dev = 0;
 			hipDeviceProp_t prop;
 			if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-				hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, FR_BIN_THREADS, dyn) != hipSuccess || per_cu < 1)
+				hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, bt, dyn) != hipSuccess || per_cu < 1)
 			{ per_cu = 1; prop.multiProcessorCount = 256; (void)hipGetLastError(); }
 			wgs = per_cu * prop.multiProcessorCount;
 			if (ncache < 48) { cache[ncache].fn = fn; cache[ncache].dyn = dyn; cache[ncache].wgs = wgs; ncache++; }
@@ -2140,11 +2167,6 @@ int launch_bin(FwdCtx &c)
 		return FR_OK;
 	};
 	int lrc = FR_OK;
-	// the packed model layout and the candidate rows are compile-time variants of the kernel (run-time tests on the pointers cost
-	// the ordinary path 5 %): packed needs both packed tensors; the rows exist when k_project stored them (foveated variants,
-	// unpacked cull pass, scales + rotations given)
-	const bool packed = a->packed_geom && a->packed_colour;
-	const bool crow = !packed && is_fov(a->variant) && a->packed_cull == nullptr && a->cov3D_precomp == nullptr;
 #define LAUNCH_BIN_PC(V, PK, CR) do { if (c.hist_mode == 2) lrc = launch((const void *)k_bin<V, 2, PK, CR>, k_bin<V, 2, PK, CR>, lds); \
 	else if (ldsh) lrc = launch((const void *)k_bin<V, 1, PK, CR>, k_bin<V, 1, PK, CR>, lds); \
 	else lrc = launch((const void *)k_bin<V, 0, PK, CR>, k_bin<V, 0, PK, CR>, lds); } while (0)
@@ -2153,7 +2175,14 @@ int launch_bin(FwdCtx &c)
 	{
 	case FR_VARIANT_ORIGINAL: LAUNCH_BIN(FR_VARIANT_ORIGINAL); break;
 	case FR_VARIANT_FOV_PCHECK_OBB:
-		if (c.fov.levels <= FR_FOV_LEVELS) LAUNCH_BIN(FR_VARIANT_FOV_PCHECK_OBB);
+		if (shared)
+		{
+			if (packed) lrc = launch((const void *)k_bin<FR_VARIANT_FOV_PCHECK_OBB, 1, true, false, FR_BIN_SHARED_THREADS>,
+				k_bin<FR_VARIANT_FOV_PCHECK_OBB, 1, true, false, FR_BIN_SHARED_THREADS>, lds);
+			else lrc = launch((const void *)k_bin<FR_VARIANT_FOV_PCHECK_OBB, 1, false, true, FR_BIN_SHARED_THREADS>,
+				k_bin<FR_VARIANT_FOV_PCHECK_OBB, 1, false, true, FR_BIN_SHARED_THREADS>, lds);
+		}
+		else if (c.fov.levels <= FR_FOV_LEVELS) LAUNCH_BIN(FR_VARIANT_FOV_PCHECK_OBB);
 		// fr_foveation.levels 5 .. 8: eight level rows per item (no packed instantiation: api.hip refuses the packed tensors)
 		else if (crow) LAUNCH_BIN_PC(FR_VARIANT_FOV8, false, true);
 		else LAUNCH_BIN_PC(FR_VARIANT_FOV8, false, false);
@@ -2167,7 +2196,7 @@ int launch_bin(FwdCtx &c)
 #undef LAUNCH_BIN
 #undef LAUNCH_BIN_PC
 	if (lrc) return lrc;
-	c.bin_wgs = nblk;
+	c.bin_wgs = nblk; c.bin_bw = bt / 64;
 	return check_launch("bin", c.stream, a->debug);
 }
 
@@ -2178,7 +2207,7 @@ int launch_emit(FwdCtx &c)
 	e.P = a->P; e.gx = c.gx; e.gy = c.gy; e.T = c.T; e.radii = a->radii; e.geom = c.geom;
 	e.highest_levels = a->highest_levels; e.tile_lv = c.img.tile_lv; e.lv_bbox = c.img.lv_bbox; e.ranges = c.img.ranges;
 	e.cursor = c.img.tile_count; e.entries = c.bin.entries; e.hist = c.img.hist;
-	e.totals = c.img.totals; e.capacity = (uint32_t)c.capacity; e.items_cap = (uint32_t)c.items_cap;
+	e.totals = c.img.totals; e.capacity = (uint32_t)c.capacity; e.items_cap = (uint32_t)c.items_cap; e.bin_bw = c.bin_bw;
 	const bool ldsh = c.hist_mode != 0; // (as k_bin counted: launch_bin)
 	const dim3 grid(c.bin_wgs), block(FR_EMIT_THREADS);
 	e.lds_tiles = (is_fov(a->variant) && ldsh) ? 1 : 0;

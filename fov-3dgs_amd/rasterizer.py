@@ -557,7 +557,8 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         # process's streams share four hardware queues, and the library's helper streams -- even idle ones, even those of the caller's
         # own stream -- cost the overlapped frames 12 % (2170 -> 1870-1920 frames/s, tools/overlap9.py) for the 1 % they give a frame
         # that has the GPU to itself (fills and the short lists' sort beside the main stream: 1725 against 1718 frames/s).
-        a.no_helper_streams = int(persistent and INFERENCE_NO_HELPER_STREAMS)
+        # (bit 1, fovraster.h: a frame of the overlapped path -- the only caller that passes `reuse` -- runs beside its neighbours' kernels)
+        a.no_helper_streams = int(persistent and INFERENCE_NO_HELPER_STREAMS) * (3 if reuse is not None else 1)
         if variant in (_native.VARIANT_PCHECK_OBB_SUM, _native.VARIANT_PCHECK_OBB_MAX, _native.VARIANT_PCHECK_OBB_LWMC) and not no_stats:
             counts = torch.empty((P,), dtype=torch.int32, device=dev)      # zeroed by fr_forward itself
             contribs = torch.empty((P,), dtype=torch.float32, device=dev)

@@ -179,9 +179,17 @@ typedef struct fr_forward_args {
 	/* != 0: every kernel and fill of the frame goes to `stream` itself -- no helper streams (by default the library forks the image /
 	 * statistics fills and the sort of the short lists onto two helper streams of its own per launch stream, which pays off for ONE
 	 * frame at a time). A host that keeps several frames in flight on several streams sets it: a process's streams share a handful of
-	 * hardware queues (four by default), and a frame's helper stream that lands in another frame's queue serialises the two. */
+	 * hardware queues (four by default), and a frame's helper stream that lands in another frame's queue serialises the two.
+	 * A bit field: bit 0 (FR_FRAME_NO_HELPER_STREAMS) is the above -- any non-zero value turns the helper streams off --, bit 1
+	 * (FR_FRAME_SHARES_GPU, only with bit 0: the value 3) says that the frame runs BESIDE other frames of the same host: its cull and
+	 * binning kernels then keep fewer waves resident per CU, which leaves registers and LDS to the neighbouring frame's emission, sort and
+	 * blend. Every output is bit-identical whatever the value; a frame alone on the GPU is fastest with bit 1 clear. The environment
+	 * variable FOVRASTER_LONE_GEOMETRY=1 (read once) makes the library ignore bit 1. */
 	int32_t no_helper_streams;
 } fr_forward_args;
+
+/* fr_forward_args.no_helper_streams */
+enum { FR_FRAME_NO_HELPER_STREAMS = 1, FR_FRAME_SHARES_GPU = 2 };
 
 enum { FR_STAGE_TILE_LEVELS = 0, FR_STAGE_PROJECT = 1, FR_STAGE_BIN = 2, FR_STAGE_TILE_SCAN = 3, FR_STAGE_EMIT = 4,
 	FR_STAGE_TILE_SORT = 5, FR_STAGE_RENDER = 6, FR_NUM_STAGES = 7 };
