@@ -158,7 +158,8 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_hvs_forward_resized", "fr_hvs_backward_resized", "fr_hvs_resized_backward_floats",
            "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward",
            "fr_quality_blocks", "fr_quality_forward", "fr_quality_finish",
-           "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap")
+           "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap",
+           "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -325,6 +326,14 @@ def load():
     lib.fr_scale_decay_backward.restype = C.c_int
     lib.fr_opacity_cap.argtypes = [C.c_int32, _FP, C.c_float, C.c_float, _FP, _FP, _FP, C.c_void_p]
     lib.fr_opacity_cap.restype = C.c_int
+    lib.fr_select_kth.argtypes = [C.c_int32, _FP, C.c_int32, C.c_int64, _FP, C.c_void_p, C.c_void_p]
+    lib.fr_select_kth.restype = C.c_int
+    lib.fr_mask_le.argtypes = [C.c_int32, _FP, C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_mask_le.restype = C.c_int
+    lib.fr_volume.argtypes = [C.c_int32, _FP, C.c_int32, _FP, C.c_void_p]
+    lib.fr_volume.restype = C.c_int
+    lib.fr_v_importance.argtypes = [C.c_int32, _FP, _FP, C.c_float, _FP, _FP, C.c_void_p]
+    lib.fr_v_importance.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -47,6 +47,10 @@ static int validate_forward(const fr_forward_args *a)
 	if (a->P > (1 << 30) || a->W > 16 * 65535 || a->H > 16 * 65535) { set_error("too large: P=%d (max 2^30) W=%d H=%d (max 65535 tiles per axis)", a->P, a->W, a->H); return FR_ERR_INVALID; }
 	if ((int64_t)((a->W + FR_TILE - 1) / FR_TILE) * ((a->H + FR_TILE - 1) / FR_TILE) >= (1 << 29)) { set_error("too many tiles (W=%d H=%d)", a->W, a->H); return FR_ERR_INVALID; }
 	if (!a->out_color) { set_error("out_color is null"); return FR_ERR_INVALID; }
+	// ORIGINAL with both statistics pointers is the counting render; one of them alone is a caller's mistake, not a request
+	if (a->variant == FR_VARIANT_ORIGINAL && (a->gaussians_count != nullptr) != (a->contributions != nullptr))
+	{ set_error("variant original: gaussians_count and contributions go together (both = the counting render, neither = the plain one); only %s is set",
+		a->gaussians_count ? "gaussians_count" : "contributions"); return FR_ERR_INVALID; }
 	if (a->P == 0) return FR_OK;
 	if (!a->means3D || !a->opacities || !a->viewmatrix || !a->projmatrix || !a->campos || !a->background || !a->radii)
 	{ set_error("a required pointer is null"); return FR_ERR_INVALID; }
@@ -314,7 +318,7 @@ int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	// frame needs them and waits (fr_forward_finish).
 	f->ax = (!a->debug && !a->no_helper_streams) ? aux_stream(stream) : nullptr;
 	hipStream_t fill_stream = stream;
-	const bool stats = has_stats(a->variant) && !a->no_stats;
+	const bool stats = (has_stats(a->variant) && !a->no_stats) || is_counting(a);
 	if (f->ax && stats)
 	{
 		if (hipEventRecord(f->ax->fork, stream) != hipSuccess || hipStreamWaitEvent(f->ax->s2, f->ax->fork, 0) != hipSuccess) { (void)hipGetLastError(); f->ax = nullptr; }
@@ -624,6 +628,42 @@ int fr_compact_rows(const fr_compact_args *a, void *stream)
 	if (a->P == 0 || a->num_tensors == 0) return FR_OK;
 	if ((uintptr_t)a->workspace % 16) { set_error("prune workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
 	return launch_compact_rows(a, (hipStream_t)stream);
+}
+
+int fr_select_kth(int32_t P, const void *values, int32_t dtype, int64_t k, void *kth_out, void *workspace, void *stream)
+{
+	if (P < 0) { set_error("select_kth: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (dtype != 0 && dtype != 1) { set_error("select_kth: unknown dtype %d (0 = fp32, 1 = int32)", dtype); return FR_ERR_INVALID; }
+	// (P = 0 has no element of any rank)
+	if (k < 0 || k >= P) { set_error("select_kth: k=%lld is not in 0..P-1=%d", (long long)k, P - 1); return FR_ERR_INVALID; }
+	if (!values || !kth_out || !workspace) { set_error("select_kth: a required pointer is null"); return FR_ERR_INVALID; }
+	if ((uintptr_t)workspace % 16) { set_error("prune workspace must be 16-byte aligned"); return FR_ERR_INVALID; }
+	return launch_select_kth(P, values, dtype, k, kth_out, workspace, (hipStream_t)stream);
+}
+
+int fr_mask_le(int32_t P, const void *values, int32_t dtype, const void *threshold_dev, uint8_t *mask, void *stream)
+{
+	if (P < 0) { set_error("mask_le: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (dtype != 0 && dtype != 1) { set_error("mask_le: unknown dtype %d (0 = fp32, 1 = int32)", dtype); return FR_ERR_INVALID; }
+	if (P > 0 && (!values || !threshold_dev || !mask)) { set_error("mask_le: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_mask_le(P, values, dtype, threshold_dev, mask, (hipStream_t)stream);
+}
+
+int fr_volume(int32_t P, const float *scaling, int32_t raw, float *volume, void *stream)
+{
+	if (P < 0) { set_error("volume: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (P > 0 && (!scaling || !volume)) { set_error("volume: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_volume(P, scaling, raw, volume, (hipStream_t)stream);
+}
+
+int fr_v_importance(int32_t P, const float *volume, const float *kth_volume_dev, float v_pow, const float *imp, float *out, void *stream)
+{
+	if (P < 0) { set_error("v_importance: bad size P=%d", P); return FR_ERR_INVALID; }
+	if (P > 0 && (!volume || !kth_volume_dev || !imp || !out)) { set_error("v_importance: a required pointer is null"); return FR_ERR_INVALID; }
+	if (P == 0) return FR_OK;
+	return launch_v_importance(P, volume, kth_volume_dev, v_pow, imp, out, (hipStream_t)stream);
 }
 
 size_t fr_densify_workspace_bytes(int32_t P) { return densify_workspace_bytes(P); }

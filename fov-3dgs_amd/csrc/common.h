@@ -52,6 +52,9 @@ namespace fr {
 // variant traits
 #define FR_VARIANT_SUM_NOSTATS 100 // internal (k_render only): pcheck_obb_sum's blend without gaussians_count / contributions
 #define FR_VARIANT_FOV8 101        // internal (k_bin only): FOV_PCHECK_OBB with fr_foveation.levels 5 .. 8 -- eight level rows per item
+#define FR_VARIANT_COUNT 102       // internal (k_render only): ORIGINAL's blend + the exact hits of every Gaussian (both statistics pointers set)
+// the counting render (LightGaussian's global significance): FR_VARIANT_ORIGINAL with gaussians_count AND contributions
+inline bool is_counting(const fr_forward_args *a) { return a->variant == FR_VARIANT_ORIGINAL && a->gaussians_count && a->contributions; }
 __host__ __device__ inline bool has_stats(int v) { return v == FR_VARIANT_PCHECK_OBB_SUM || v == FR_VARIANT_PCHECK_OBB_MAX || v == FR_VARIANT_PCHECK_OBB_LWMC; }
 __host__ __device__ inline bool has_backward(int v) { return v == FR_VARIANT_ORIGINAL || has_stats(v); }
 // variants that bin by eccentricity level (tile level map, level filter): RF and the shared-model baseline
@@ -511,6 +514,10 @@ int launch_prune_metric(int P, int kind, const float *contribs, const int32_t *c
 int launch_prune_select(int P, const float *metrics, int64_t k, uint8_t *mask, void *ws, hipStream_t stream);
 int launch_compact_plan(int P, const uint8_t *mask, int invert, int32_t *count_out, void *ws, hipStream_t stream);
 int launch_compact_rows(const fr_compact_args *a, hipStream_t stream);
+int launch_select_kth(int P, const void *values, int dtype, int64_t k, void *kth_out, void *ws, hipStream_t stream);
+int launch_mask_le(int P, const void *values, int dtype, const void *threshold, uint8_t *mask, hipStream_t stream); // significance.hip
+int launch_volume(int P, const float *scaling, int raw, float *volume, hipStream_t stream);
+int launch_v_importance(int P, const float *volume, const float *kth_volume, float v_pow, const float *imp, float *out, hipStream_t stream);
 size_t densify_workspace_bytes(int P); // densify.hip
 int launch_densify_stats(int P, const float *grad, const uint8_t *filter, float *accum, float *denom, hipStream_t stream);
 int launch_densify_plan(const fr_densify_plan_args *a, hipStream_t stream);

@@ -16,6 +16,8 @@
 //                     radix select, 4 x 8 bits from the top: LDS digit histograms of the keys that match the digits
 //                     found so far (one row of 256 counts per workgroup), then one workgroup that adds the rows, finds
 //                     the digit that holds rank k and leaves (threshold so far, rank inside it) for the next pass
+//   k_select_tail     fr_select_kth (LightGaussian's percentile thresholds, significance.hip): the same four passes over fp32
+//                     or int32 values, then the threshold key turned back into the value of rank k
 //   k_prune_tie_count / k_prune_scan / k_prune_write
 //                     rows with key == threshold per tile, their exclusive running sum in index order, and the mask:
 //                     key < T, or key == T and fewer than r equal keys before it
@@ -64,13 +66,19 @@ __device__ __forceinline__ uint32_t prune_key(float m)
 	return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// ... and of int32 values (fr_select_kth with dtype 1: summed hit counts exceed 2^24, so no detour through float): the words
+// travel through the same loads as the floats' bit patterns, and the key is the value with its sign bit flipped
+template <int DT>
+__device__ __forceinline__ uint32_t prune_key_of(float m) { return DT == 1 ? __float_as_uint(m) ^ 0x80000000u : prune_key(m); }
+
 // the keys of rows i .. i + 3 (0 where i + j >= P) and, as the return value, how many of them exist
+template <int DT = 0>
 __device__ __forceinline__ int prune_load_keys(const float *__restrict__ metrics, size_t i, size_t P, bool aligned, uint32_t key[PRUNE_PER_THREAD])
 {
 	if (i + PRUNE_PER_THREAD <= P && aligned)
 	{
 		const float4 v = *(const float4 *)(metrics + i);
-		key[0] = prune_key(v.x); key[1] = prune_key(v.y); key[2] = prune_key(v.z); key[3] = prune_key(v.w);
+		key[0] = prune_key_of<DT>(v.x); key[1] = prune_key_of<DT>(v.y); key[2] = prune_key_of<DT>(v.z); key[3] = prune_key_of<DT>(v.w);
 		return PRUNE_PER_THREAD;
 	}
 	int n = 0;
@@ -78,7 +86,7 @@ __device__ __forceinline__ int prune_load_keys(const float *__restrict__ metrics
 	for (int j = 0; j < PRUNE_PER_THREAD; j++)
 	{
 		const bool valid = i + j < P;
-		key[j] = valid ? prune_key(metrics[i + j]) : 0u;
+		key[j] = valid ? prune_key_of<DT>(metrics[i + j]) : 0u;
 		n += valid;
 	}
 	return n;
@@ -139,6 +147,7 @@ __device__ __forceinline__ void prune_hist_add(uint32_t *s_hist, uint32_t key, b
 // counts[blockIdx.x][d] = keys of this workgroup's tiles whose digits above `shift` equal those of state[0] and whose
 // digit at `shift` is d. Tiles that every thread reads as one 16-byte load go PRUNE_HIST_UNROLL at a time, all loads
 // issued before the first key is counted; the last tile, and everything when metrics is not 16-byte aligned, one by one.
+template <int DT>
 __global__ void __launch_bounds__(256) k_prune_hist(int P, int64_t tiles, int shift, const float *__restrict__ metrics,
 	const uint32_t *__restrict__ state, uint32_t *__restrict__ counts, int aligned)
 {
@@ -160,10 +169,10 @@ __global__ void __launch_bounds__(256) k_prune_hist(int P, int64_t tiles, int sh
 #pragma unroll
 			for (int u = 0; u < PRUNE_HIST_UNROLL; u++)
 			{
-				prune_hist_add(s_hist, prune_key(v[u].x), true, prefix, himask, shift, lane);
-				prune_hist_add(s_hist, prune_key(v[u].y), true, prefix, himask, shift, lane);
-				prune_hist_add(s_hist, prune_key(v[u].z), true, prefix, himask, shift, lane);
-				prune_hist_add(s_hist, prune_key(v[u].w), true, prefix, himask, shift, lane);
+				prune_hist_add(s_hist, prune_key_of<DT>(v[u].x), true, prefix, himask, shift, lane);
+				prune_hist_add(s_hist, prune_key_of<DT>(v[u].y), true, prefix, himask, shift, lane);
+				prune_hist_add(s_hist, prune_key_of<DT>(v[u].z), true, prefix, himask, shift, lane);
+				prune_hist_add(s_hist, prune_key_of<DT>(v[u].w), true, prefix, himask, shift, lane);
 			}
 			continue;
 		}
@@ -172,7 +181,7 @@ __global__ void __launch_bounds__(256) k_prune_hist(int P, int64_t tiles, int sh
 			const int64_t tile = tile0 + (int64_t)u * gridDim.x;
 			if (tile >= tiles) break;
 			uint32_t key[PRUNE_PER_THREAD];
-			const int n = prune_load_keys(metrics, (size_t)tile * PRUNE_TILE + (size_t)t * PRUNE_PER_THREAD, (size_t)P, aligned != 0, key);
+			const int n = prune_load_keys<DT>(metrics, (size_t)tile * PRUNE_TILE + (size_t)t * PRUNE_PER_THREAD, (size_t)P, aligned != 0, key);
 #pragma unroll
 			for (int j = 0; j < PRUNE_PER_THREAD; j++) prune_hist_add(s_hist, key[j], j < n, prefix, himask, shift, lane);
 		}
@@ -325,6 +334,22 @@ int launch_prune_metric(int P, int kind, const float *contribs, const int32_t *c
 	return check_launch("prune_metric", stream, false);
 }
 
+// the four radix passes: state = {key of the element of 1-based rank `rank`, that rank inside the run of equal keys}
+template <int DT>
+static void prune_radix_passes(int P, const PruneLayout &L, const float *values, uint32_t rank, void *ws, hipStream_t stream)
+{
+	char *base = (char *)ws;
+	uint32_t *counts = (uint32_t *)(base + L.hist), *state = (uint32_t *)(base + L.state);
+	// a histogram workgroup takes PRUNE_HIST_UNROLL tiles at a time, so that many fewer workgroups than tiles, at most PRUNE_HIST_WGS
+	const unsigned tiles = (unsigned)L.tiles, want = (tiles + PRUNE_HIST_UNROLL - 1) / PRUNE_HIST_UNROLL, wgs = want < PRUNE_HIST_WGS ? want : PRUNE_HIST_WGS;
+	const int aligned = (uintptr_t)values % 16 == 0;
+	for (int shift = 24; shift >= 0; shift -= 8)
+	{
+		hipLaunchKernelGGL(k_prune_hist<DT>, dim3(wgs), dim3(256), 0, stream, P, L.tiles, shift, values, state, counts, aligned);
+		hipLaunchKernelGGL(k_prune_pick, dim3(1), dim3(256), 0, stream, (int)wgs, shift, rank, counts, state);
+	}
+}
+
 int launch_prune_select(int P, const float *metrics, int64_t k, uint8_t *mask, void *ws, hipStream_t stream)
 {
 	if (k == 0 || k == P) // nothing or everything: no order needed
@@ -335,21 +360,37 @@ int launch_prune_select(int P, const float *metrics, int64_t k, uint8_t *mask, v
 	}
 	const PruneLayout L = prune_layout(P);
 	char *base = (char *)ws;
-	uint32_t *counts = (uint32_t *)(base + L.hist), *state = (uint32_t *)(base + L.state), *tie = (uint32_t *)(base + L.tie);
-	// a histogram workgroup takes PRUNE_HIST_UNROLL tiles at a time, so that many fewer workgroups than tiles, at most PRUNE_HIST_WGS
-	const unsigned tiles = (unsigned)L.tiles, want = (tiles + PRUNE_HIST_UNROLL - 1) / PRUNE_HIST_UNROLL, wgs = want < PRUNE_HIST_WGS ? want : PRUNE_HIST_WGS;
+	uint32_t *state = (uint32_t *)(base + L.state), *tie = (uint32_t *)(base + L.tie);
+	const unsigned tiles = (unsigned)L.tiles;
 	const int aligned = (uintptr_t)metrics % 16 == 0, mask_aligned = (uintptr_t)mask % 4 == 0;
-	for (int shift = 24; shift >= 0; shift -= 8)
-	{
-		hipLaunchKernelGGL(k_prune_hist, dim3(wgs), dim3(256), 0, stream, P, L.tiles, shift, metrics, state, counts, aligned);
-		hipLaunchKernelGGL(k_prune_pick, dim3(1), dim3(256), 0, stream, (int)wgs, shift, (uint32_t)k, counts, state);
-	}
+	prune_radix_passes<0>(P, L, metrics, (uint32_t)k, ws, stream);
 	int rc = check_launch("prune_select", stream, false);
 	if (rc) return rc;
 	hipLaunchKernelGGL(k_prune_tie_count, dim3(tiles), dim3(256), 0, stream, P, metrics, state, tie, aligned);
 	hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(256), 0, stream, L.tiles, tie, (int32_t *)nullptr);
 	hipLaunchKernelGGL(k_prune_write, dim3(tiles), dim3(256), 0, stream, P, metrics, state, tie, mask, aligned, mask_aligned);
 	return check_launch("prune_write", stream, false);
+}
+
+// fr_select_kth: the threshold key the four passes leave in state[0], turned back into a value (one thread)
+__global__ void k_select_tail(const uint32_t *__restrict__ state, int dtype, uint32_t *__restrict__ kth_out)
+{
+	const uint32_t key = state[0];
+	uint32_t bits;
+	if (dtype == 1) bits = key ^ 0x80000000u;
+	else if (key == 0xffffffffu) bits = 0x7fc00000u;        // the NaN class: a quiet NaN
+	else if (key == 0x80000000u) bits = 0u;                 // the zero class (-0 and +0): +0.0
+	else bits = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+	*kth_out = bits;
+}
+
+int launch_select_kth(int P, const void *values, int dtype, int64_t k, void *kth_out, void *ws, hipStream_t stream)
+{
+	const PruneLayout L = prune_layout(P);
+	if (dtype == 1) prune_radix_passes<1>(P, L, (const float *)values, (uint32_t)k + 1u, ws, stream);
+	else prune_radix_passes<0>(P, L, (const float *)values, (uint32_t)k + 1u, ws, stream);
+	hipLaunchKernelGGL(k_select_tail, dim3(1), dim3(1), 0, stream, (const uint32_t *)((const char *)ws + L.state), dtype, (uint32_t *)kth_out);
+	return check_launch("select_kth", stream, false);
 }
 
 int launch_compact_plan(int P, const uint8_t *mask, int invert, int32_t *count_out, void *ws, hipStream_t stream)

@@ -197,12 +197,21 @@ template <int VARIANT, int PPL>
 __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 {
 	// (FR_VARIANT_SUM_NOSTATS, internal: pcheck_obb_sum for a caller that drops the statistics, fr_forward_args.no_stats)
-	constexpr bool CUTOFF = VARIANT != FR_VARIANT_ORIGINAL;
+	// (FR_VARIANT_COUNT, internal: ORIGINAL's arithmetic -- same image, final_T, n_contrib bit for bit -- plus gaussians_count[i] = the
+	// (pixel, Gaussian i) pairs that were accumulated: LightGaussian's renderCUDA_count, compress-diff-gaussian-rasterization
+	// cuda_rasterizer/forward.cu:378-501, whose `gaussian_count[id]++` is a non-atomic read-modify-write from all 256 threads of every
+	// tile; here the count is exact: what that statement gives when the pixels run one at a time)
+	constexpr bool COUNT = VARIANT == FR_VARIANT_COUNT;
+	constexpr bool CUTOFF = VARIANT != FR_VARIANT_ORIGINAL && !COUNT;
 	constexpr bool SUM = VARIANT == FR_VARIANT_PCHECK_OBB_SUM;   // contributions += alpha*T, count per fetched entry
 	constexpr bool PMAX = VARIANT == FR_VARIANT_PCHECK_OBB_MAX;  // contributions = max alpha*T, count per in-support pixel
 	constexpr bool LWMC = VARIANT == FR_VARIANT_PCHECK_OBB_LWMC; // per-pixel loss to its max-contribution Gaussian
 	constexpr bool FETCHCNT = SUM || LWMC;                       // gaussians_count per fetched entry (256-rounds)
-	constexpr bool NEEDID = SUM || PMAX || LWMC;
+	constexpr bool NEEDID = SUM || PMAX || LWMC || COUNT;
+	// COUNT: an entry's hits are wave-uniform (two ballots per row pair) and reach memory as one integer atomic of lane 0 per (wave,
+	// entry) with a non-zero count, as _max's counts do. Measured against it (tools/significance_bench.py --lanes-lib, tools/scratch/
+	// count_lanes.patch): lane j keeps the running count of entry j of the batch and the wave adds a batch's counts with ONE vector
+	// atomic instruction -- 1.304 ms (p10-p90 1.294-1.323) against 1.312 ms (1.308-1.329) per S-6M frame: inside the spread, not kept.
 	constexpr bool AUX = VARIANT != FR_VARIANT_PCHECK_OBB; // final_T / n_contrib kept for backward
 	static_assert(PPL == 2, "work items encode two bands per tile");
 	constexpr int HP = PPL / 2;
@@ -381,11 +390,13 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 					c += __popcll(__ballot(t.inx[h] && S[h].T.x > 0.0f)) + __popcll(__ballot(t.iny[h] && S[h].T.y > 0.0f));
 				if (st == 0 && c != 0) atomicAdd(&a.gaussians_count[sid[j]], c);
 			}
+			int hits = 0;
 #pragma unroll
 			for (int h = 0; h < HP; h++)
 			{
 				v2f w; bool ax, ay;
 				blend2k<true>(S[h], t.okx[h], t.oky[h], t.e[h], t.col, w, ax, ay);
+				if (COUNT) hits += __popcll(__ballot(ax)) + __popcll(__ballot(ay));
 				if (AUX)
 				{
 					last[2 * h] = ax ? (uint32_t)(base + j + 1) : last[2 * h];
@@ -400,6 +411,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 					best_w[2 * h + 1] = by ? w.y : best_w[2 * h + 1]; best_id[2 * h + 1] = by ? sid[j] : best_id[2 * h + 1];
 				}
 			}
+			if (COUNT && st == 0 && hits != 0) atomicAdd(&a.gaussians_count[sid[j]], hits);
 			if (PMAX)
 			{
 				if (__any(any_contrib))
@@ -980,6 +992,20 @@ __global__ void __launch_bounds__(64) k_render_mmfr(const RenderArgs a)
 	}
 }
 
+// important_score of the counting render (rasterize_points.cu:178, forward.cu:474: `important_score[id] += con_o.w` per accumulated
+// pair, an fp32 running sum in an order nobody fixed): here the value that sum approximates, hits * opacity, formed exactly in
+// double (int32 -> double is exact) and rounded once. The opacity is the one the blend used: through the sigmoid with
+// raw_activations, from the packed row with the packed layout.
+__global__ void __launch_bounds__(256) k_count_score(int P, const int32_t *__restrict__ hits, const float *__restrict__ opacities,
+	const float *__restrict__ packed_geom, int raw, float *__restrict__ score)
+{
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= (size_t)P) return;
+	const float op_in = packed_geom ? packed_geom[16 * i + 12] : opacities[i];
+	const float op = raw ? act_opacity(op_in) : op_in;
+	score[i] = (float)((double)hits[i] * (double)op);
+}
+
 int launch_render(FwdCtx &c)
 {
 	const fr_forward_args *a = c.a;
@@ -1007,7 +1033,9 @@ int launch_render(FwdCtx &c)
 #define FR_LAUNCH_RENDER(V, UNUSED_) hipLaunchKernelGGL((k_render<V, PPL>), dim3(n_items), dim3(64), 0, c.stream, r)
 	switch (a->variant)
 	{
-	case FR_VARIANT_ORIGINAL: FR_LAUNCH_RENDER(FR_VARIANT_ORIGINAL, true); break;
+	case FR_VARIANT_ORIGINAL:
+		if (is_counting(a)) FR_LAUNCH_RENDER(FR_VARIANT_COUNT, true); else FR_LAUNCH_RENDER(FR_VARIANT_ORIGINAL, true);
+		break;
 	case FR_VARIANT_PCHECK_OBB_SUM:
 		if (a->no_stats) FR_LAUNCH_RENDER(FR_VARIANT_SUM_NOSTATS, false); else FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB_SUM, false);
 		break;
@@ -1021,6 +1049,14 @@ int launch_render(FwdCtx &c)
 		break;
 	}
 #undef FR_LAUNCH_RENDER
+	if (is_counting(a))
+	{
+		const int rc = check_launch("render", c.stream, a->debug);
+		if (rc) return rc;
+		hipLaunchKernelGGL(k_count_score, dim3((unsigned)((a->P + 255) / 256)), dim3(256), 0, c.stream, a->P, a->gaussians_count, a->opacities,
+			a->packed_geom, a->raw_activations, a->contributions);
+		return check_launch("count_score", c.stream, a->debug);
+	}
 	return check_launch("render", c.stream, a->debug);
 }
 

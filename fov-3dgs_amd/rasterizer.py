@@ -438,9 +438,11 @@ class FrameInFlight:
 def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                    shs_dcs=None, highest_levels=None, gaze=(0.5, 0.5), alpha=0.05, persistent=False, loss_map=None,
                    sh_rest=None, packed=None, cur_level=0.0, raw_activations=False, list_consumed=None, no_stats=False, blend_pairs=None,
-                   on_stream=None, reuse=None, reuse_key=None, foveation=None):
-    """First half of a forward call on the current stream -> FrameInFlight. on_stream: the caller HAS made this stream (and its
-    device) current and says so (saves the lookups). persistent=True: the workspaces are the grow-only
+                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False):
+    """First half of a forward call on the current stream -> FrameInFlight. count (variant original only): the counting render of
+    LightGaussian's global-significance pruning -- the call also returns gaussians_count (exact hits per Gaussian) and the
+    important_score (fovraster.h, fr_forward_args.gaussians_count); image and radii are those of the plain call.
+    on_stream: the caller HAS made this stream (and its device) current and says so (saves the lookups). persistent=True: the workspaces are the grow-only
     set of this (device, stream, thread) (valid until the next call there); otherwise they stay reserved for as long as the
     `lease` of the result is referenced.
     reuse / reuse_key (the overlapped inference path): `reuse` is a dict the caller keeps per internal stream; when its "key" equals
@@ -559,7 +561,9 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         # that has the GPU to itself (fills and the short lists' sort beside the main stream: 1725 against 1718 frames/s).
         # (bit 1, fovraster.h: a frame of the overlapped path -- the only caller that passes `reuse` -- runs beside its neighbours' kernels)
         a.no_helper_streams = int(persistent and INFERENCE_NO_HELPER_STREAMS) * (3 if reuse is not None else 1)
-        if variant in (_native.VARIANT_PCHECK_OBB_SUM, _native.VARIANT_PCHECK_OBB_MAX, _native.VARIANT_PCHECK_OBB_LWMC) and not no_stats:
+        if count and variant != _native.VARIANT_ORIGINAL:
+            raise RuntimeError("fovraster: the counting render is the original rasterizer's (compress_diff_gaussian_rasterization)")
+        if (variant in (_native.VARIANT_PCHECK_OBB_SUM, _native.VARIANT_PCHECK_OBB_MAX, _native.VARIANT_PCHECK_OBB_LWMC) and not no_stats) or count:
             counts = torch.empty((P,), dtype=torch.int32, device=dev)      # zeroed by fr_forward itself
             contribs = torch.empty((P,), dtype=torch.float32, device=dev)
             a.gaussians_count, a.contributions = counts.data_ptr(), contribs.data_ptr()

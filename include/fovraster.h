@@ -117,6 +117,18 @@ typedef struct fr_forward_args {
 	int32_t *radii;              /* [P] */
 	int32_t *gaussians_count;    /* RS: [P], else NULL (zeroed by the call, then accumulated) */
 	float *contributions;        /* RS: [P], else NULL (zeroed by the call, then accumulated) */
+	/* FR_VARIANT_ORIGINAL with BOTH of them set is the counting render of LightGaussian's global-significance pruning
+	 * (compress-diff-gaussian-rasterization, count_gaussians / renderCUDA_count, cuda_rasterizer/forward.cu:378-501); exactly
+	 * one of them set is FR_ERR_INVALID. Image, radii, final_T and n_contrib are those of the plain call bit for bit, and both
+	 * arrays are written in full:
+	 *   gaussians_count[i] = the (pixel, Gaussian i) pairs the blend accumulated (past the power > 0, alpha < 1/255 and
+	 *                        T (1 - alpha) < 1e-4 tests), exact;
+	 *   contributions[i]   = important_score: (float)((double)gaussians_count[i] * (double)opacity[i]), the opacity as the blend
+	 *                        used it (through the sigmoid with raw_activations, from packed_geom with the packed layout).
+	 * A deviation from the reference on purpose: its two statements (forward.cu:473-474, `gaussian_count[id]++` and
+	 * `important_score[id] += con_o.w`) are NON-atomic read-modify-writes from all 256 threads of every tile, so its output
+	 * is not a function of its input (lanes that hit the same entry collapse into one increment). Here: what the statements
+	 * give when the pixels run one at a time, the same bits on every run (integer atomics only). */
 	/* workspaces */
 	fr_resize_fn geometry_resize;
 	fr_resize_fn binning_resize;
@@ -577,6 +589,27 @@ typedef struct fr_compact_args {
 
 int fr_compact_plan(int32_t P, const uint8_t *mask, int32_t invert, int32_t *count_out, void *workspace, void *stream);
 int fr_compact_rows(const fr_compact_args *args, void *stream);
+
+/* LightGaussian's global-significance pruning (csrc/significance.hip, csrc/prune.hip; replaces LightGaussian/prune.py:112-128
+ * calculate_v_imp_score and scene/gaussian_model.py:776-782 prune_gaussians: two full torch.sorts for one element each, five
+ * elementwise passes and a comparison). The per-view counts and scores come from the counting render (fr_forward_args.
+ * gaussians_count). As above: caller's stream, no host synchronisation, no allocation, workspace = fr_prune_workspace_bytes(P),
+ * P = 0 launches nothing, every output is one bit pattern.
+ *   select_kth    *kth_out (a DEVICE word) = the element of rank k (0-based, ascending) under the total order of
+ *                 fr_prune_select_lowest: what torch.sort(values, stable=True)[0][k] holds (a tie at zero gives +0.0, the NaN
+ *                 class a quiet NaN). dtype: 0 = fp32, 1 = int32 (compared as integers: summed counts exceed 2^24). k outside
+ *                 0 .. P-1 is FR_ERR_INVALID.
+ *   mask_le       mask[i] = values[i] <= *threshold_dev: the IEEE comparison for fp32, so a NaN row is never marked
+ *                 (gaussian_model.py:781). All rows tied with the threshold are marked: the number of ones is known on the
+ *                 device only (fr_compact_plan counts them).
+ *   volume        volume[i] = (s0 * s1) * s2 of scaling [P,3], each product rounded once (torch.prod(get_scaling, dim=1));
+ *                 raw != 0: s = exp(raw scaling) first, the device expression of fr_activate_forward.
+ *   v_importance  out[i] = powf(volume[i] / *kth_volume_dev, v_pow) * imp[i] (prune.py:126-127), the division correctly
+ *                 rounded, nothing contracted. out may be volume. */
+int fr_select_kth(int32_t P, const void *values, int32_t dtype, int64_t k, void *kth_out, void *workspace, void *stream);
+int fr_mask_le(int32_t P, const void *values, int32_t dtype, const void *threshold_dev, uint8_t *mask, void *stream);
+int fr_volume(int32_t P, const float *scaling, int32_t raw, float *volume, void *stream);
+int fr_v_importance(int32_t P, const float *volume, const float *kth_volume_dev, float v_pow, const float *imp, float *out, void *stream);
 
 /* The quality gate of the pruning loop (csrc/quality.hip; replaces test_ssim_loss / test_psnr_loss, fov3dgs/prune.py:137-174 --
  * two renders, the torch ssim and psnr and a host synchronisation per view -- and utils/image_utils.py:14-19 mse / psnr).
