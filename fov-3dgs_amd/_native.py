@@ -159,7 +159,8 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward",
            "fr_quality_blocks", "fr_quality_forward", "fr_quality_finish",
            "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap",
-           "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance")
+           "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance",
+           "fr_vq_workspace_bytes", "fr_vq_nearest", "fr_vq_gather", "fr_vq_update", "fr_vq_replace", "fr_pack_bits", "fr_unpack_bits")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -334,6 +335,21 @@ def load():
     lib.fr_volume.restype = C.c_int
     lib.fr_v_importance.argtypes = [C.c_int32, _FP, _FP, C.c_float, _FP, _FP, C.c_void_p]
     lib.fr_v_importance.restype = C.c_int
+    lib.fr_vq_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.fr_vq_workspace_bytes.restype = C.c_size_t
+    _rows = [C.c_int64, C.c_int32, C.c_int32, _FP, C.c_int64, _FP, C.c_int32]  # n, K, D, feats, N, rows, rows64
+    lib.fr_vq_nearest.argtypes = _rows + [_FP, _FP, _FP, C.c_void_p]
+    lib.fr_vq_nearest.restype = C.c_int
+    lib.fr_vq_gather.argtypes = _rows + [_FP, _FP, C.c_int32, _FP, _FP, _FP, C.c_float, _FP, C.c_void_p]
+    lib.fr_vq_gather.restype = C.c_int
+    lib.fr_vq_update.argtypes = _rows + [_FP, _FP, C.c_float, C.c_float, _FP, _FP, _FP, C.c_void_p]
+    lib.fr_vq_update.restype = C.c_int
+    lib.fr_vq_replace.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_int64, _FP, C.c_int32, _FP, _FP, _FP, _FP, C.c_void_p]
+    lib.fr_vq_replace.restype = C.c_int
+    lib.fr_pack_bits.argtypes = [C.c_int64, C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_pack_bits.restype = C.c_int
+    lib.fr_unpack_bits.argtypes = [C.c_int64, C.c_int32, _FP, _FP, C.c_void_p]
+    lib.fr_unpack_bits.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -27,7 +27,7 @@ the number of pruned rows is only known on the device: the compaction plan's cou
 synchronisation of a prune after its renders.
 
 GPU tensors only: there is no CPU fallback. Not here: the fine-tune loop (the vanilla rasterizer, loss_utils and optim.Adam
-of this package), distill_train.py, vectree quantisation."""
+of this package), distill_train.py. The stage after it, vectree quantisation, is fov3dgs_amd.vectree."""
 import math
 
 import torch

@@ -611,6 +611,40 @@ int fr_mask_le(int32_t P, const void *values, int32_t dtype, const void *thresho
 int fr_volume(int32_t P, const float *scaling, int32_t raw, float *volume, void *stream);
 int fr_v_importance(int32_t P, const float *volume, const float *kth_volume_dev, float v_pow, const float *imp, float *out, void *stream);
 
+/* LightGaussian's VecTree SH vector quantisation (csrc/vq.hip; replaces LightGaussian/vectree/vq.py:262-299 EuclideanCodebook.forward
+ * in the configuration of vectree.py:44-51 -- one head, no projection, decay EMA, no dead-code threshold, temperature 0 -- the loop
+ * of vectree.py:196-204 and the bit matrix of vectree.py:120-126). As above: caller's stream, no host synchronisation, no
+ * allocation, no float atomics, every output one bit pattern, run after run.
+ *   Input rows: row i of a call is feats[rows[i]] (feats: [N, D] fp32, row stride D; rows: n int32 (rows64 = 0) or int64 indices,
+ *   or NULL: feats[i], N >= n). An index outside 0 .. N-1 is clamped into that range, never followed. weights, where given, are
+ *   indexed like feats (weights[rows[i]]). 1 <= K <= 65536, 1 <= D <= 64, n < 2^31. workspace: fr_vq_workspace_bytes(n, K, D,
+ *   training) bytes, 16-byte aligned; training = 0 suffices for nearest / gather, update and replace need training = 1.
+ *   nearest   ind[i] = argmin_c ||x_i - e_c|| (vq.py:276-277: -cdist, argmax), ranked by ||e_c||^2 - 2 x_i . e_c with the dot product
+ *             accumulated on the exact f32 matrix instruction (a fmaf chain over ascending d). An exact tie of two scores goes to
+ *             the lower code. The n x K matrix is never formed.
+ *   gather    quantize[i] = embed[ind[i]] (vq.py:280; to_half: rounded through fp16, vectree.py:95), dist2[i] = sum_d (x - e)^2
+ *             from the differences, *loss = float(loss_weight * sum dist2 / (n D)) summed in double in a fixed order (vq.py:405-407).
+ *             Each of quantize, dist2, loss may be NULL; feats may be NULL when only quantize is asked for.
+ *   update    the training step on the codebook AS ASSIGNED (ind from nearest, before this call): w' = w n / sum w (vq.py:264; 1
+ *             without weights), cluster_size = cluster_size decay + (1 - decay) sum_{ind = c} w' (:285-289), embed_sum = sum w' x
+ *             (:292-294) in ascending row position, smoothed = (cluster_size + eps) / (sum cluster_size + K eps) sum cluster_size
+ *             (:296), embed = embed decay + (1 - decay) embed_sum / smoothed (:298). A code with no member decays by `decay`.
+ *   replace   the k <= 64 codes of smallest cluster_size are overwritten by the k input rows of largest weight, smallest with
+ *             largest and so on (vectree.py:202-204, two torch.topk). Ties go to the lowest index in both selections.
+ *   pack_bits / unpack_bits   `bits` (1 .. 16) per value, MSB first, values back to back: np.packbits of the reference's dec2bin
+ *             matrix. out holds (count bits + 7) / 8 bytes, the last one zero-padded. */
+size_t fr_vq_workspace_bytes(int64_t n, int32_t K, int32_t D, int32_t training);
+int fr_vq_nearest(int64_t n, int32_t K, int32_t D, const float *feats, int64_t N, const void *rows, int32_t rows64, const float *embed,
+	int32_t *ind, void *workspace, void *stream);
+int fr_vq_gather(int64_t n, int32_t K, int32_t D, const float *feats, int64_t N, const void *rows, int32_t rows64, const float *embed,
+	const int32_t *ind, int32_t to_half, float *quantize, float *dist2, float *loss, float loss_weight, void *workspace, void *stream);
+int fr_vq_update(int64_t n, int32_t K, int32_t D, const float *feats, int64_t N, const void *rows, int32_t rows64, const float *weights,
+	const int32_t *ind, float decay, float eps, float *embed, float *cluster_size, void *workspace, void *stream);
+int fr_vq_replace(int64_t n, int32_t K, int32_t D, int32_t k, const float *feats, int64_t N, const void *rows, int32_t rows64,
+	const float *weights, float *embed, const float *cluster_size, void *workspace, void *stream);
+int fr_pack_bits(int64_t count, int32_t bits, const int32_t *values, uint8_t *out, void *stream);
+int fr_unpack_bits(int64_t count, int32_t bits, const uint8_t *in, int32_t *values, void *stream);
+
 /* The quality gate of the pruning loop (csrc/quality.hip; replaces test_ssim_loss / test_psnr_loss, fov3dgs/prune.py:137-174 --
  * two renders, the torch ssim and psnr and a host synchronisation per view -- and utils/image_utils.py:14-19 mse / psnr).
  * img / target: [C,H,W] fp32 device tensors. Everything runs on `stream` with no host synchronisation, no allocation and no
