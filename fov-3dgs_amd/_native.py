@@ -63,6 +63,21 @@ class Foveation(C.Structure):
                 ("real_viewing_distance", C.c_float), ("start_blend", C.c_float), ("blend_width", C.c_float)]
 
 
+class FovState(C.Structure):
+    """fr_fov_state: what the state-keeping foveated forward (fr_forward_begin_fov_keep) leaves for fr_backward_fov_appearance"""
+    _fields_ = [("size", C.c_uint32), ("variant", C.c_int32), ("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("levels", C.c_int32), ("num_rendered", C.c_int32), ("num_items", C.c_int32),
+                ("start_blend", C.c_float), ("blend_width", C.c_float),
+                ("geometry", C.c_void_p), ("binning", C.c_void_p), ("image", C.c_void_p)]
+
+
+class BackwardFovArgs(C.Structure):
+    """fr_backward_fov_args"""
+    _fields_ = [("size", C.c_uint32), ("debug", C.c_int32), ("state", C.POINTER(FovState)),
+                ("background", _FP), ("dL_dpix", _FP), ("dL_dopacities", _FP), ("dL_dshs_dcs", _FP), ("dL_dlevel_colours", _FP),
+                ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p)), ("blend_pairs", _FP)]
+
+
 class BackwardArgs(C.Structure):
     _fields_ = [
         ("variant", C.c_int32), ("P", C.c_int32), ("D", C.c_int32), ("M", C.c_int32), ("R", C.c_int32),
@@ -160,13 +175,18 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_quality_blocks", "fr_quality_forward", "fr_quality_finish",
            "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap",
            "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance",
-           "fr_vq_workspace_bytes", "fr_vq_nearest", "fr_vq_gather", "fr_vq_update", "fr_vq_replace", "fr_pack_bits", "fr_unpack_bits")
+           "fr_vq_workspace_bytes", "fr_vq_nearest", "fr_vq_gather", "fr_vq_update", "fr_vq_replace", "fr_pack_bits", "fr_unpack_bits",
+           "fr_forward_begin_fov_keep", "fr_forward_fov_keep_call", "fr_geometry_bytes_fov_keep", "fr_image_bytes_fov_keep",
+           "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
 # ... and the foveation settings (fr_foveation): has_foveation(); without them only the reference's constants render
 FOVEATION_EXPORTS = ("fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov")
-OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS
+# ... and the foveated renderer's appearance backward pass: has_fov_backward(); without it appearance_only on that renderer raises
+FOV_BACKWARD_EXPORTS = ("fr_forward_begin_fov_keep", "fr_forward_fov_keep_call", "fr_geometry_bytes_fov_keep", "fr_image_bytes_fov_keep",
+                        "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance")
+OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS + FOV_BACKWARD_EXPORTS
 
 _lib = None
 
@@ -283,6 +303,21 @@ def load():
         lib.fr_geometry_level_colours_hi.restype = C.c_void_p
         lib.fr_pack_colour_fov.argtypes = [C.c_int32, _FP, _FP, C.c_int32, _FP, C.c_void_p]
         lib.fr_pack_colour_fov.restype = C.c_int
+    if has_fov_backward(lib):
+        lib.fr_forward_begin_fov_keep.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(FovState),
+                                                  C.POINTER(C.c_void_p)]
+        lib.fr_forward_begin_fov_keep.restype = C.c_int
+        lib.fr_forward_fov_keep_call.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(FovState)]
+        lib.fr_forward_fov_keep_call.restype = C.c_int
+        lib.fr_geometry_bytes_fov_keep.argtypes = [C.c_int32, C.c_int32]
+        lib.fr_geometry_bytes_fov_keep.restype = C.c_size_t
+        lib.fr_image_bytes_fov_keep.argtypes = [C.c_int32, C.c_int32]
+        lib.fr_image_bytes_fov_keep.restype = C.c_size_t
+        for n in ("fr_image_fov_state_T", "fr_image_fov_state_n"):
+            getattr(lib, n).argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+            getattr(lib, n).restype = C.c_void_p
+        lib.fr_backward_fov_appearance.argtypes = [C.POINTER(BackwardFovArgs)]
+        lib.fr_backward_fov_appearance.restype = C.c_int
     lib.fr_forward_finish.argtypes = [C.c_void_p]
     lib.fr_forward_finish.restype = C.c_int
     lib.fr_backward_prefill.argtypes = [C.POINTER(BackwardArgs), C.c_void_p]
@@ -366,6 +401,12 @@ def has_foveation(lib=None):
     """the loaded library takes fr_foveation settings (else: only the reference's constants, and anything else is refused)"""
     lib = load() if lib is None else lib
     return all(hasattr(lib, n) for n in FOVEATION_EXPORTS)
+
+
+def has_fov_backward(lib=None):
+    """the loaded library has the foveated renderer's appearance backward pass (fr_backward_fov_appearance)"""
+    lib = load() if lib is None else lib
+    return all(hasattr(lib, n) for n in FOV_BACKWARD_EXPORTS)
 
 
 def last_error():

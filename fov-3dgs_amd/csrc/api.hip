@@ -259,20 +259,36 @@ struct fr_frame
 	bool scan_enqueued = false;    // the kernel that writes the pinned totals block is on the stream ...
 	bool totals_read = false;      // ... and the host has read what it wrote
 	bool empty = false;            // P == 0: nothing left to do
+	fr_fov_state *keep_state = nullptr; // the state-keeping foveated forward: filled by fr_forward_finish
 	// every exit that abandons the frame joins the helper stream first: the caller may free or reuse out_color / the
 	// statistics arrays / the workspaces as soon as the call has returned
 	void join_aux() { if (aux_pending && ax) (void)hipStreamWaitEvent(c.stream, ax->join2, 0); aux_pending = false; }
 	~fr_frame() { join_aux(); release_pinned(pin, scan_enqueued && !totals_read, c.stream); }
 };
 
-extern "C" {
+namespace fr {
 
-int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **out)
+// what the state-keeping foveated forward refuses, before anything is enqueued (the message names the field)
+static int validate_fov_keep(const fr_forward_args *a, const fr_foveation *fov, const fr_fov_state *state)
+{
+	if (!state) { set_error("fr_fov_state: state is null"); return FR_ERR_INVALID; }
+	if (state->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", state->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
+	if (a->variant != FR_VARIANT_FOV_PCHECK_OBB)
+	{ set_error("fr_forward_args.variant is %d: the state-keeping forward is for variant %d (fov_pcheck_obb) only", a->variant, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
+	if (fov && fov->levels > FR_FOV_LEVELS)
+	{ set_error("fr_foveation.levels is %d: the appearance backward pass keeps one row of sums per Gaussian, i.e. at most %d levels", fov->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
+	if (a->packed_geom || a->packed_colour || a->packed_cull)
+	{ set_error("packed_geom / packed_colour / packed_cull: the state-keeping forward renders from the ordinary tensors (a packed model is inference-only)"); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
+static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, bool keep, fr_frame **out)
 {
 	if (!out) { set_error("null frame handle"); return FR_ERR_INVALID; }
 	*out = nullptr;
 	int rc = validate_forward(a);
 	if (rc) return rc;
+	if (keep) { rc = validate_fov_keep(a, fov, keep_state); if (rc) return rc; }
 	if (ext && ext->size < sizeof(fr_forward_ext)) { set_error("fr_forward_ext.size is %u, expected at least %u", ext->size, (unsigned)sizeof(fr_forward_ext)); return FR_ERR_INVALID; }
 	rc = validate_foveation(a, fov);
 	if (rc) return rc;
@@ -288,6 +304,15 @@ int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	c.a = a; c.stream = stream;
 	c.visibility = ext ? ext->visibility : nullptr; // (read here: ext need not outlive this call)
 	c.fov = fov_params(fov);                        // (likewise: the settings travel in the kernels' arguments)
+	c.keep = keep ? 1 : 0;
+	f->keep_state = keep ? keep_state : nullptr;
+	if (keep)
+	{
+		const uint32_t sz = keep_state->size;
+		memset(keep_state, 0, sizeof(fr_fov_state));
+		keep_state->size = sz; keep_state->variant = a->variant; keep_state->P = a->P; keep_state->W = a->W; keep_state->H = a->H;
+		keep_state->levels = c.fov.levels; keep_state->start_blend = c.fov.start_blend; keep_state->blend_width = c.fov.blend_width;
+	}
 	if (a->P == 0)
 	{
 		// reference: RasterizeGaussiansCUDA returns the zero-initialised image when P == 0
@@ -302,11 +327,20 @@ int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	c.focal_y = a->H / (2.0f * a->tanfovy);
 	c.focal_x = a->W / (2.0f * a->tanfovx);
 
-	char *gptr = a->geometry_resize(a->resize_user[0], carve_geom(a->variant, (size_t)a->P, nullptr, c.fov.levels).bytes);
-	char *iptr = a->image_resize(a->resize_user[2], carve_image(a->variant, a->W, a->H, nullptr).bytes);
+	char *gptr = a->geometry_resize(a->resize_user[0], keep ? carve_fov_keep_geom((size_t)a->P, nullptr, c.fov.levels).bytes
+		: carve_geom(a->variant, (size_t)a->P, nullptr, c.fov.levels).bytes);
+	char *iptr = a->image_resize(a->resize_user[2], keep ? carve_fov_keep_image(a->W, a->H, nullptr).bytes : carve_image(a->variant, a->W, a->H, nullptr).bytes);
 	if (!gptr || !iptr) { set_error("geometry/image resize callback returned null"); return FR_ERR_ALLOC; }
 	c.geom = carve_geom(a->variant, (size_t)a->P, gptr, c.fov.levels);
 	c.img = carve_image(a->variant, a->W, a->H, iptr);
+	if (keep)
+	{
+		// (behind the plain call's arrays: fr_geometry_bytes_fov_keep / fr_image_bytes_fov_keep)
+		const FovKeepImage ki = carve_fov_keep_image(a->W, a->H, iptr);
+		c.keep_T = ki.final_T; c.keep_n = ki.n_contrib;
+		c.keep_acc = carve_fov_keep_geom((size_t)a->P, gptr, c.fov.levels).acc;
+		keep_state->geometry = gptr; keep_state->image = iptr;
+	}
 
 	// RF: the two level states of a two-level tile are blended by different waves, which ADD their halves to the image: those
 	// tiles' pixels are cleared by k_project's waves beside their stream over the cloud (preprocess.hip). Before that: a fill
@@ -363,6 +397,20 @@ int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	if (!c.scan_fused) { rc = launch_tile_scan(c); if (rc) return rc; } // (else: k_bin's last workgroup did it)
 	*out = f; guard.f = nullptr;
 	return FR_OK;
+}
+
+} // namespace fr
+
+extern "C" {
+
+int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **out)
+{
+	return forward_begin(a, ext, fov, nullptr, false, out);
+}
+
+int fr_forward_begin_fov_keep(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state, fr_frame **out)
+{
+	return forward_begin(a, ext, fov, state, true, out);
 }
 
 int fr_forward_finish(fr_frame *f)
@@ -445,6 +493,12 @@ int fr_forward_finish(fr_frame *f)
 	if (a->num_rendered > 0) { rc = launch_tile_sort(c); if (rc) return rc; }
 	mark(FR_STAGE_RENDER);
 	f->join_aux(); // the fills of the frame's head
+	if (c.keep)
+	{
+		// the backward pass adds into the rows of sums of the frame's items: they start as zeros
+		rc = launch_fov_keep_clear(c); if (rc) return rc;
+		f->keep_state->binning = bptr; f->keep_state->num_rendered = a->num_rendered; f->keep_state->num_items = c.n_items;
+	}
 	rc = launch_render(c);
 	mark(FR_NUM_STAGES);
 	return rc;
@@ -467,6 +521,23 @@ int fr_forward_fov_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_
 	if (rc) return rc;
 	return fr_forward_finish(f);
 }
+
+int fr_forward_fov_keep_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state)
+{
+	fr_frame *f = nullptr;
+	const int rc = fr_forward_begin_fov_keep(a, ext, fov, state, &f);
+	if (rc) return rc;
+	return fr_forward_finish(f);
+}
+
+size_t fr_geometry_bytes_fov_keep(int32_t P, int32_t levels)
+{
+	if (P < 0 || levels < 2 || levels > FR_FOV_LEVELS) { set_error("bad geometry_bytes_fov_keep arguments (levels 2 .. %d)", FR_FOV_LEVELS); return 0; }
+	return carve_fov_keep_geom((size_t)P, nullptr, levels).bytes;
+}
+size_t fr_image_bytes_fov_keep(int32_t W, int32_t H) { return carve_fov_keep_image(W, H, nullptr).bytes; }
+const float *fr_image_fov_state_T(int32_t W, int32_t H, const char *image) { return carve_fov_keep_image(W, H, (char *)image).final_T; }
+const uint32_t *fr_image_fov_state_n(int32_t W, int32_t H, const char *image) { return carve_fov_keep_image(W, H, (char *)image).n_contrib; }
 
 int fr_forward_ext_call(fr_forward_args *a, const fr_forward_ext *ext) { return fr_forward_fov_call(a, ext, nullptr); }
 
@@ -759,6 +830,29 @@ int fr_backward_appearance(const fr_backward_args *a)
 	if (a->dL_dsh && (!a->shs || a->colors_precomp)) { set_error("backward_appearance: dL_dsh needs shs (with colors_precomp ask for dL_dcolor)"); return FR_ERR_INVALID; }
 	if (a->raw_activations && a->cov3D_precomp) { set_error("raw_activations needs scales + rotations"); return FR_ERR_INVALID; }
 	return launch_backward_appearance(a);
+}
+
+int fr_backward_fov_appearance(const fr_backward_fov_args *a)
+{
+	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
+	if (a->size < sizeof(fr_backward_fov_args)) { set_error("fr_backward_fov_args.size is %u, expected at least %u", a->size, (unsigned)sizeof(fr_backward_fov_args)); return FR_ERR_INVALID; }
+	const fr_fov_state *st = a->state;
+	if (!st) { set_error("backward_fov_appearance: state is null"); return FR_ERR_INVALID; }
+	if (st->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", st->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
+	if (st->variant != FR_VARIANT_FOV_PCHECK_OBB)
+	{ set_error("backward_fov_appearance: state.variant is %d, not %d (fov_pcheck_obb): not the state of a state-keeping foveated forward", st->variant, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
+	if (st->levels < 2 || st->levels > FR_FOV_LEVELS)
+	{ set_error("backward_fov_appearance: state.levels is %d, not in 2..%d (levels 5 .. 8 would need a second row of sums)", st->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
+	if (st->P < 0 || st->W <= 0 || st->H <= 0 || st->num_rendered < 0 || st->num_items < 0
+		|| (int64_t)st->num_items > 4 * (int64_t)((st->W + FR_TILE - 1) / FR_TILE) * ((st->H + FR_TILE - 1) / FR_TILE))
+	{ set_error("backward_fov_appearance: state holds bad sizes (P=%d W=%d H=%d num_rendered=%d num_items=%d)", st->P, st->W, st->H, st->num_rendered, st->num_items); return FR_ERR_INVALID; }
+	if (st->P == 0) return FR_OK;
+	if (!st->geometry || !st->image || (st->num_rendered > 0 && !st->binning)) { set_error("backward_fov_appearance: state.geometry / image / binning is null"); return FR_ERR_INVALID; }
+	if (!a->dL_dpix) { set_error("backward_fov_appearance: dL_dpix is null"); return FR_ERR_INVALID; }
+	if (!a->background) { set_error("backward_fov_appearance: background is null"); return FR_ERR_INVALID; }
+	if (!a->dL_dopacities) { set_error("backward_fov_appearance: dL_dopacities is null"); return FR_ERR_INVALID; }
+	if (!a->dL_dshs_dcs) { set_error("backward_fov_appearance: dL_dshs_dcs is null"); return FR_ERR_INVALID; }
+	return launch_backward_fov_appearance(a);
 }
 
 int fr_backward_prefill(const fr_backward_args *a, void *fill_stream)

@@ -109,12 +109,28 @@ struct BwdRenderArgs {
 	uint32_t *pairs; // optional diagnostic (fr_backward_args.blend_pairs): [T], (band, entry) pairs evaluated, or null
 };
 
+// The foveated lean tile pass (fr_backward_fov_appearance) takes the work items of k_render_fov: tile << 3 | band | level state << 1 |
+// two-level << 2. What it needs beside the plain pass's arguments:
+struct BwdFovArgs : BwdRenderArgs {
+	const float4 *lvl;              // the items' level rows (r, g, b, opacity) of the levels 0 .. 3 (GeomWS::lvl)
+	const float *tile_lv;           // [5][T] (ImageWS::tile_lv)
+	int T;
+	float start_blend, blend_width; // fr_foveation
+};
+
+// One work item of the tile pass: k_render_bwd's and k_render_bwd_fov's kernels are this function.
 // LEAN (fr_backward_appearance): only the colour sums and M00 are formed and folded (fold8), into the same components of the row
 // (0, 1, 2 and 8); the five other moments and the products that serve only them are left out. Walk, staging, skip tests and the
 // recovery of T are the same code.
-template <bool CUTOFF, bool LEAN = false>
-__global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
+// FOV (LEAN only; RF forward.cu:262-609 has no backward: the arithmetic is backward.cu:399-557's applied to k_render_fov's blend): the
+// item carries ONE level state of its tile -- the entries take part with that level's row (opacity and colour: lvl[4 item + lev]), the
+// state's final_T / n_contrib come from its plane of the state-keeping forward, dL/dpixel is weighted with the state's share of the
+// pixel (w1 or 1 - w1 in a two-level tile: geometry and settings only, a constant of the derivative), the upper state skips the
+// Gaussians that do not exist at its level (forward.cu:399), and the four sums go to components 4 lev .. 4 lev + 3 of the row.
+template <bool CUTOFF, bool LEAN, bool FOV, typename Args>
+__device__ __forceinline__ void render_bwd_item(const Args &a)
 {
+	static_assert(!FOV || (LEAN && CUTOFF), "the foveated tile pass is the lean one");
 	constexpr int PPL = 2;
 	constexpr int NV = LEAN ? 4 : 9; // sums per (band, entry) pair
 	__shared__ float4 s0[64];  // x, y, conic a, conic b
@@ -135,6 +151,20 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 	if (n == 0) return;
 	const size_t plane = (size_t)a.W * a.H;
 	const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
+	// FOV: the item's level state
+	bool two_level = false, upper = false;
+	int lev = 0;
+	float tlf = 0.0f, tgx = 0.0f, tgy = 0.0f, L2f = 0.0f;
+	if constexpr (FOV)
+	{
+		two_level = (item & 4u) != 0; upper = (item & 2u) != 0;
+		tlf = a.tile_lv[a.T + tile];                                  // tile_min
+		tgx = a.tile_lv[2 * (size_t)a.T + tile]; tgy = a.tile_lv[3 * (size_t)a.T + tile];
+		L2f = tlf + 1.0f;
+		lev = f2i(tlf) + (upper ? 1 : 0);
+		if (lev < 0 || lev >= FR_FOV_LEVELS) return;                  // (four level rows, four quarters of the row of sums)
+	}
+	const size_t state_plane = (FOV && upper) ? plane : 0;
 
 	// per pixel (the lane's two pixels as packed pairs, v_pk_* arithmetic): transmittance behind the current entry and the
 	// colour accumulated behind it, as its product A with dL/dpixel
@@ -149,12 +179,26 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 		pyp[k] = (float)py;
 		const bool inside = px < a.W && py < a.H;
 		const size_t pid = (size_t)a.W * py + px;
-		Tfin[k] = inside ? a.final_T[pid] : 0.0f;
-		lastc[k] = inside ? (int)a.n_contrib[pid] : 0;
+		Tfin[k] = inside ? a.final_T[state_plane + pid] : 0.0f;
+		lastc[k] = inside ? (int)a.n_contrib[state_plane + pid] : 0;
 		wave_last = max(wave_last, lastc[k]);
 		dp0[k] = inside ? a.dL_dpix[pid] : 0.0f;
 		dp1[k] = inside ? a.dL_dpix[plane + pid] : 0.0f;
 		dp2[k] = inside ? a.dL_dpix[2 * plane + pid] : 0.0f;
+		if constexpr (FOV)
+		{
+			if (two_level)
+			{
+				// the state's share of the pixel, as k_render_fov forms it (RF forward.cu:455-470): w1 = 1 - smoothstep
+				const float est = tlf + ((float)lx * tgx + (float)tile_row<PPL>(tid, k) * tgy) / (float)FR_TILE;
+				float x = fabsf(est - ((float)f2i(tlf) + a.start_blend)) / a.blend_width;
+				x = fmaxf(0.0f, fminf(1.0f, x));
+				const float bT = 3 * x * x - 2 * x * x * x;
+				const float w1 = 1 - bT;
+				const float w = upper ? (1.f - w1) : w1;
+				dp0[k] *= w; dp1[k] *= w; dp2[k] *= w;
+			}
+		}
 	}
 	T = Tfin;
 	bgdot = bg0 * dp0 + bg1 * dp1 + bg2 * dp2;
@@ -168,13 +212,28 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 	// registers while this one is processed
 	float4 p0 = make_float4(0, 0, 0, 0), p1 = p0;
 	float2 p2 = make_float2(0, 0);
+	float phl = 0.0f; // FOV: the entry's highest level
 	auto fetch = [&](int e)
 	{
 		const uint32_t id = a.point_list[range.x + e]; // the item: its record and its row of gradient sums share the index
 		const float4 *r = a.rec + 3 * (size_t)id;
-		p0 = r[0]; p1 = r[1];
-		p2 = make_float2(r[2].x, __uint_as_float(id));
+		if constexpr (FOV)
+		{
+			// RF: (conic c, highest level, -, -) in the record; opacity and colour in the state's level row
+			p0 = r[0];
+			const float4 r1 = r[1], lv = a.lvl[(size_t)id * FR_FOV_LEVELS + lev];
+			p1 = make_float4(r1.x, lv.w, lv.x, lv.y);
+			p2 = make_float2(lv.z, __uint_as_float(id));
+			phl = r1.y;
+		}
+		else
+		{
+			p0 = r[0]; p1 = r[1];
+			p2 = make_float2(r[2].x, __uint_as_float(id));
+		}
 	};
+	// the component of the row a sum goes to: (r, g, b, M00) of level `lev` are components 4 lev .. 4 lev + 3 of the foveated row
+	auto row_comp = [&](const int comp) { if constexpr (FOV) return 4 * lev + (comp == 8 ? 3 : comp); else return comp; };
 	// the forward blend's skip tests (k_render: outside the support, alpha < 1/255) as its ONE threshold on q = -power: the very same
 	// expression, so that the backward pass takes the gradient of exactly the pairs the forward pass blended
 	auto q_threshold = [&](float opacity, float &lq) { lq = logf(255.0f * opacity); return lq >= 0.0f ? (CUTOFF ? fminf(4.5f, lq) : lq) : 0.0f; };
@@ -213,7 +272,10 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 			// (power < -4.5, alpha < 1/255 <=> power < -ln(255 opacity)), see splat_reaches()
 			const float thr_a = -lq - 0.01f;
 			const float thr = CUTOFF ? fmaxf(-4.5f, thr_a) : thr_a;
-			reach = __ballot(staged && lq >= 0.0f && band_reaches<PPL>(wv, tx, ty, p0.x, p0.y, p0.z, p0.w, p1.x, thr));
+			// (FOV: the upper state skips the Gaussians that do not exist at its level, as k_render_fov does: RF forward.cu:399)
+			bool exists = true;
+			if constexpr (FOV) exists = !upper || !((phl + 1.0f) < L2f);
+			reach = __ballot(staged && exists && lq >= 0.0f && band_reaches<PPL>(wv, tx, ty, p0.x, p0.y, p0.z, p0.w, p1.x, thr));
 			npairs += (uint32_t)__popcll(reach);
 			}
 		if (top - 64 - lane > 0) fetch(top - 64 - 1 - lane);
@@ -306,7 +368,7 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 					float val;
 					if constexpr (LEAN) val = fold8(pend, v, lane, e, comp, writer);
 					else val = fold18(pend, v, lane, e, comp, writer);
-					if (writer) atomicAdd(a.acc + 16 * (size_t)(e ? row : pend_row) + comp, val); // eighteen (LEAN: eight) lanes, two cache lines
+					if (writer) atomicAdd(a.acc + 16 * (size_t)(e ? row : pend_row) + row_comp(comp), val); // eighteen (LEAN: eight) lanes, two cache lines
 					have_pend = false;
 				}
 			}
@@ -319,12 +381,16 @@ __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a)
 			const float none[NV] = {};
 			int e, comp; bool writer;
 			const float val = fold8(pend, none, lane, e, comp, writer);
-			if (writer && e == 0) atomicAdd(a.acc + 16 * (size_t)pend_row + comp, val);
+			if (writer && e == 0) atomicAdd(a.acc + 16 * (size_t)pend_row + row_comp(comp), val);
 		}
 	}
 	else if (have_pend) fold_one(pend, pend_row); // an odd entry is left
 	if (a.pairs != nullptr && lane == 0 && npairs != 0) atomicAdd(a.pairs + tile, npairs);
 }
+
+template <bool CUTOFF, bool LEAN = false>
+__global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a) { render_bwd_item<CUTOFF, LEAN, false>(a); }
+__global__ void __launch_bounds__(64, 5) k_render_bwd_fov(const BwdFovArgs a) { render_bwd_item<true, true, true>(a); }
 
 // ---- per-Gaussian chain rule ------------------------------------------------------------------
 // Written from the matrix form of the forward pass rather than entry by entry.
@@ -1202,6 +1268,135 @@ int launch_backward_appearance(const fr_backward_args *a)
 	const int rc2 = check_launch("appearance_bwd", stream, a->debug);
 	// one piece: every row of the dense outputs is complete behind this launch (fovraster.h: the single-piece rule of range_done)
 	if (!rc2 && a->range_done != nullptr && !a->row_sparse) a->range_done(a->range_user, 0, 0, a->P);
+	mark(2);
+	return rc2;
+}
+
+// ---- foveated appearance pass (fr_backward_fov_appearance) ----------------------------------------------------------------------
+// Per visible-list item: the sixteen sums k_render_bwd_fov left -- level l's (r, g, b, M00) in quarter l of the item's row -- become
+//   dL/dopacities[g][l]     = M00                       (the saturation min(0.99, o G) is not differentiated: backward.cu:497-541),
+//   dL/dlevel_colours[g][l] = the colour sums (optional),
+//   dL/dshs_dcs[g][l]       = SH_C0 * colour sums, zero for a channel the forward pass clamped at that level: the level rows keep
+//                             max(0, .) (k_bin's colour_item), so a stored 0 is a clamped channel (a pre-clamp value of exactly 0 is
+//                             taken as clamped).
+// The level rows are read for the levels of the item's level range only (GeomWS::lrange: the others were never evaluated, and no
+// tile blended them: their sums are exact zeros). The row of sums is cleared again: a second backward pass over the same forward
+// state starts from zeros, as fr_backward_appearance's does. Items that landed in no tile keep the zeros of the fill.
+struct BwdFovAppArgs {
+	float4 *acc;
+	const float4 *lvl;
+	const uint32_t *vis_list, *vis_count, *lrange;
+	float *dL_dopacities, *dL_dshs_dcs, *dL_dlevel_colours; // [P, L], [P, L, 3], [P, L, 3] or null
+	int L;
+};
+
+__global__ void __launch_bounds__(256) k_fov_appearance_bwd(const BwdFovAppArgs a)
+{
+	const int V = (int)*a.vis_count;
+	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x))
+	{
+		const uint32_t lr = a.lrange[i];
+		if (lr == FR_ITEM_NONE) continue;
+		const int lo = (int)(lr & 0xffu), hi = (int)((lr >> 8) & 0xffu);
+		const size_t g = (size_t)a.vis_list[i];
+#pragma unroll
+		for (int l = 0; l < FR_FOV_LEVELS; l++)
+		{
+			if (l >= a.L) break;
+			const float4 s = a.acc[4 * (size_t)i + l];
+			a.acc[4 * (size_t)i + l] = make_float4(0.f, 0.f, 0.f, 0.f);
+			const bool used = l >= lo && l <= hi;
+			const float4 c = used ? a.lvl[4 * (size_t)i + l] : make_float4(0.f, 0.f, 0.f, 0.f);
+			const size_t o = g * (size_t)a.L + l;
+			FR_ST(a.dL_dopacities + o, s.w);
+			FR_ST(a.dL_dshs_dcs + 3 * o, c.x > 0.0f ? FR_SH_C0 * s.x : 0.0f);
+			FR_ST(a.dL_dshs_dcs + 3 * o + 1, c.y > 0.0f ? FR_SH_C0 * s.y : 0.0f);
+			FR_ST(a.dL_dshs_dcs + 3 * o + 2, c.z > 0.0f ? FR_SH_C0 * s.z : 0.0f);
+			if (a.dL_dlevel_colours != nullptr)
+			{
+				FR_ST(a.dL_dlevel_colours + 3 * o, s.x); FR_ST(a.dL_dlevel_colours + 3 * o + 1, s.y); FR_ST(a.dL_dlevel_colours + 3 * o + 2, s.z);
+			}
+		}
+	}
+}
+
+__global__ void __launch_bounds__(256) k_clear_item_rows(float4 *acc, const uint32_t *vis_count)
+{
+	const size_t n = 4 * (size_t)*vis_count;
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+int launch_fov_keep_clear(FwdCtx &c)
+{
+	const size_t quads = 4 * (size_t)c.a->P;
+	const unsigned blocks = (unsigned)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048);
+	hipLaunchKernelGGL(k_clear_item_rows, dim3(blocks), dim3(256), 0, c.stream, c.keep_acc, c.geom.slab_ctr + 1);
+	return check_launch("clear_item_rows", c.stream, c.a->debug);
+}
+
+// One k_fill_zero over the dense outputs in front of the tile pass (as fr_backward_appearance: they are 28 L bytes a Gaussian), the
+// tile pass over the forward's work items, the per-Gaussian pass. Everything on the caller's stream, no synchronisation.
+int launch_backward_fov_appearance(const fr_backward_fov_args *a)
+{
+	const fr_fov_state *st = a->state;
+	hipStream_t stream = (hipStream_t)a->stream;
+	const int gx = (st->W + FR_TILE - 1) / FR_TILE, gy = (st->H + FR_TILE - 1) / FR_TILE, T = gx * gy;
+	const size_t P = (size_t)st->P;
+	const int L = st->levels;
+	GeomWS geom = carve_geom(FR_VARIANT_FOV_PCHECK_OBB, P, (char *)st->geometry, L);
+	ImageWS img = carve_image(FR_VARIANT_FOV_PCHECK_OBB, st->W, st->H, (char *)st->image);
+	BinWS bin = carve_bin(st->num_rendered, (char *)st->binning);
+	const FovKeepGeom kg = carve_fov_keep_geom(P, (char *)st->geometry, L);
+	const FovKeepImage ki = carve_fov_keep_image(st->W, st->H, (char *)st->image);
+	auto mark = [&](int i) { if (a->stage_events && a->stage_events[i]) (void)hipEventRecord((hipEvent_t)a->stage_events[i], stream); };
+	{
+		struct { void *p; size_t words; } fills[] = { { a->dL_dopacities, P * L }, { a->dL_dshs_dcs, 3 * P * L }, { a->dL_dlevel_colours, 3 * P * L } };
+		FillArgs fa; fa.n = 0;
+		for (auto &f : fills)
+			if (f.p)
+			{
+				if (((uintptr_t)f.p & 15) != 0)
+				{
+					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
+					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+					continue;
+				}
+				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
+			}
+		if (fa.n)
+		{
+			const size_t quads = (3 * P * L + 3) / 4;
+			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
+			hipLaunchKernelGGL(k_fill_zero, dim3(blocks), dim3(256), 0, stream, fa);
+			const int rcf = check_launch("fill_zero (fov appearance)", stream, a->debug);
+			if (rcf) return rcf;
+		}
+	}
+	mark(0);
+	if (st->num_rendered > 0 && st->num_items > 0)
+	{
+		BwdFovArgs r;
+		r.W = st->W; r.H = st->H; r.gx = gx; r.ranges = img.ranges; r.render_items = img.render_items; r.n_items = (uint32_t)st->num_items;
+		r.point_list = bin.point_list; r.rec = geom.rec;
+		r.bg = a->background; r.final_T = ki.final_T; r.n_contrib = ki.n_contrib; r.dL_dpix = a->dL_dpix;
+		r.acc = (float *)kg.acc;
+		r.pairs = a->blend_pairs;
+		r.lvl = geom.lvl; r.tile_lv = img.tile_lv; r.T = T; r.start_blend = st->start_blend; r.blend_width = st->blend_width;
+		if (r.pairs != nullptr)
+		{
+			const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
+			if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+		}
+		hipLaunchKernelGGL(k_render_bwd_fov, dim3(r.n_items), dim3(64), 0, stream, r);
+		const int rc0 = check_launch("render_bwd_fov", stream, a->debug);
+		if (rc0) return rc0;
+	}
+	mark(1);
+	BwdFovAppArgs p;
+	p.acc = kg.acc; p.lvl = geom.lvl; p.vis_list = geom.vis_list; p.vis_count = geom.slab_ctr + 1; p.lrange = geom.lrange;
+	p.dL_dopacities = a->dL_dopacities; p.dL_dshs_dcs = a->dL_dshs_dcs; p.dL_dlevel_colours = a->dL_dlevel_colours; p.L = L;
+	const int pblocks = (int)((P + 255) / 256);
+	hipLaunchKernelGGL(k_fov_appearance_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
+	const int rc2 = check_launch("fov_appearance_bwd", stream, a->debug);
 	mark(2);
 	return rc2;
 }

@@ -195,6 +195,35 @@ __host__ __device__ inline ImageWS carve_image(int variant, int W, int H, char *
 	return s;
 }
 
+// What the state-keeping foveated forward (fr_forward_begin_fov_keep) keeps for fr_backward_fov_appearance, BEHIND the workspaces of
+// the inference call: no array of theirs moves, and fr_geometry_bytes_fov / fr_image_bytes answer what they answered.
+struct FovKeepGeom {
+	float4 *acc;        // [4P] one 64-byte row of sums per item: level l's (dL/d colour r, g, b, M00) in quarter l (k_render_bwd_fov adds,
+	                    //      k_fov_appearance_bwd reads and clears; the forward call clears the rows of its items)
+	size_t bytes;
+};
+__host__ __device__ inline FovKeepGeom carve_fov_keep_geom(size_t P, char *base, int levels)
+{
+	FovKeepGeom g; size_t off = align_up(carve_geom(FR_VARIANT_FOV_PCHECK_OBB, P, nullptr, levels).bytes);
+	g.acc = (float4 *)(base + off); off = align_up(off + P * 4 * sizeof(float4));
+	g.bytes = off + 256;
+	return g;
+}
+struct FovKeepImage {
+	float *final_T;      // [2][W*H] per level state (plane 0: a single-level tile's state, state 1 of a two-level tile; plane 1: state 2):
+	uint32_t *n_contrib; // [2][W*H] the transmittance the state ended with, the 1-based list position of its last contributor
+	size_t bytes;
+};
+__host__ __device__ inline FovKeepImage carve_fov_keep_image(int W, int H, char *base)
+{
+	FovKeepImage s; size_t off = align_up(carve_image(FR_VARIANT_FOV_PCHECK_OBB, W, H, nullptr).bytes);
+	const size_t N = (size_t)W * H;
+	s.final_T = (float *)(base + off); off = align_up(off + 2 * N * sizeof(float));
+	s.n_contrib = (uint32_t *)(base + off); off = align_up(off + 2 * N * sizeof(uint32_t));
+	s.bytes = off + 256;
+	return s;
+}
+
 // Binning workspace (per (Gaussian,tile) instance), laid out for a CAPACITY of D instances (>= the frame's number: the
 // forward call may size it before the count is known, see fr_forward). point_list comes first, so that its address -- all
 // the backward pass and the introspection entry points need -- does not depend on the capacity.
@@ -487,6 +516,10 @@ struct FwdCtx {
 	uint32_t totals_seq;       // this frame's sequence number for that word
 	float focal_x, focal_y;
 	FovParams fov;      // foveated variants: the call's fr_foveation (the reference's constants without one)
+	int keep = 0;               // the state-keeping foveated forward: k_render_fov<2, true> leaves the level states' final_T / n_contrib ...
+	float *keep_T = nullptr;    // ... in these planes (FovKeepImage) ...
+	uint32_t *keep_n = nullptr;
+	float4 *keep_acc = nullptr; // ... and the items' rows of gradient sums (FovKeepGeom::acc) are cleared
 	GeomWS geom;
 	ImageWS img;
 	BinWS bin;
@@ -531,6 +564,9 @@ int launch_render(FwdCtx &c);
 int launch_backward(const fr_backward_args *a);
 // fr_backward_appearance: the lean tile pass (colour sums and M00 only) and k_appearance_bwd instead of the chain rule
 int launch_backward_appearance(const fr_backward_args *a);
+// fr_backward_fov_appearance: the foveated lean tile pass over the forward's work items and k_fov_appearance_bwd
+int launch_backward_fov_appearance(const fr_backward_fov_args *a);
+int launch_fov_keep_clear(FwdCtx &c); // the state-keeping forward: the rows of sums of the frame's items start as zeros
 // whole: clear every tensor in full (fr_backward_prefill: the caller's zeros come before a backward call that is told about them);
 // else the narrow tensors only where no 32-row group holds a visible Gaussian (the rest of them is k_preprocess_bwd's, backward.hip)
 int launch_gradient_fill(const fr_backward_args *a, hipStream_t fs, bool events, bool whole);

@@ -520,8 +520,16 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 // pulling the items from 64 queues 182 us (a wave cannot migrate: at the tail some SIMDs still hold eight busy waves
 // while others are empty; handing the slot back after every item: 152 us, i.e. the hardware's placement of fresh
 // workgroups IS the load balancer); s_setprio by round or by remaining list length: nothing.
-template <int PPL>
-__global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
+//
+// KEEP (the state-keeping forward of fr_forward_begin_fov_keep, for fr_backward_fov_appearance): the same blend -- same products, same
+// atomicAdd meeting of the two rounded halves, so the image is the inference image bit for bit -- that also leaves, per pixel and
+// level state, what k_render<..., AUX> leaves per pixel: the transmittance the state ended with and the 1-based list position of its
+// last contributor, in plane 0 (the state of a single-level tile, state 1 of a two-level tile) or plane 1 (state 2) of
+// RenderArgs::final_T / n_contrib ([2][W*H] each here). A state-1 pixel that starts finished (est > L2) keeps T = 1, n = 0. The
+// instantiation has launch bounds of its own (two more registers for the positions: it need not hold eight waves); the inference
+// instantiation's code is what it was.
+template <int PPL, bool KEEP = false>
+__global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArgs a)
 {
 	static_assert(PPL == 2, "work items encode two bands per tile");
 	constexpr int HP = PPL / 2;
@@ -574,6 +582,9 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 		}
 #pragma unroll
 		for (int h = 0; h < HP; h++) S1[h].C0 = S1[h].C1 = S1[h].C2 = (v2f){ 0.f, 0.f };
+		uint32_t last[KEEP ? PPL : 1]; // KEEP: 1-based list position of the pixel's last contributor (n_contrib)
+#pragma unroll
+		for (int k = 0; k < (KEEP ? PPL : 1); k++) last[k] = 0;
 
 #ifdef FR_TILE_TIMERS
 		const uint64_t tm0 = wall_clock64(); uint32_t tm_proc = 0, tm_batches = 0; uint64_t tm_loop = 0, tm_sync = 0;
@@ -690,7 +701,17 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 #pragma unroll
 				for (int g = 0; g < FR_RENDER_GROUP; g++)
 #pragma unroll
-					for (int h = 0; h < HP; h++) blend2k<true>(S1[h], t[g].inx[h], t[g].iny[h], t[g].e[h], t[g].c1);
+					for (int h = 0; h < HP; h++)
+					{
+						if constexpr (KEEP)
+						{
+							v2f w; bool ax, ay;
+							blend2k<true>(S1[h], t[g].inx[h], t[g].iny[h], t[g].e[h], t[g].c1, w, ax, ay);
+							last[2 * h] = ax ? (uint32_t)(base + jj[g] + 1) : last[2 * h];
+							last[2 * h + 1] = ay ? (uint32_t)(base + jj[g] + 1) : last[2 * h + 1];
+						}
+						else blend2k<true>(S1[h], t[g].inx[h], t[g].iny[h], t[g].e[h], t[g].c1);
+					}
 			}
 #ifdef FR_TILE_TIMERS
 			tm_loop += wall_clock64() - tq1;
@@ -698,7 +719,7 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 		}
 
 #ifdef FR_TILE_TIMERS
-		if (lane == 0)
+		if (!KEEP && lane == 0)
 		{
 			// developer build only (tools/tile_cycles.py): per-ITEM records in the otherwise unused final_T / n_contrib arrays
 			const uint32_t G = 4u * (uint32_t)a.T, b = idx;
@@ -715,6 +736,11 @@ __global__ void __launch_bounds__(64, 8) k_render_fov(const RenderArgs a)
 			if (!inside[k]) continue;
 			const size_t pid = (size_t)a.W * (size_t)(ty * FR_TILE + tile_row<PPL>(tid, k)) + px;
 			const float t1 = S1[k >> 1].Tk[k & 1];
+			if constexpr (KEEP)
+			{
+				const size_t sp = upper ? plane + pid : pid; // the state's plane
+				a.final_T[sp] = t1; a.n_contrib[sp] = last[k];
+			}
 			const float o0 = fmaf(bg0, t1, S1[k >> 1].C0[k & 1]), o1 = fmaf(bg1, t1, S1[k >> 1].C1[k & 1]), o2 = fmaf(bg2, t1, S1[k >> 1].C2[k & 1]);
 			if (two_level)
 			{
@@ -1015,6 +1041,7 @@ int launch_render(FwdCtx &c)
 	r.start_blend = c.fov.start_blend; r.blend_width = c.fov.blend_width;
 	r.tile_lv = c.img.tile_lv; r.tile_order = c.img.tile_order; r.T = c.T; r.bg = a->background; r.out_color = a->out_color;
 	r.final_T = c.img.final_T; r.n_contrib = c.img.n_contrib;
+	if (c.keep) { r.final_T = c.keep_T; r.n_contrib = c.keep_n; } // the state planes behind the image workspace (carve_fov_keep)
 	r.gaussians_count = a->gaussians_count; r.contributions = a->contributions; r.loss_map = a->loss_map;
 	r.render_items = c.img.render_items; r.totals = c.img.totals; r.capacity = (uint32_t)c.capacity; r.cur_level = a->cur_level;
 	constexpr int PPL = 2;
@@ -1045,7 +1072,8 @@ int launch_render(FwdCtx &c)
 	case FR_VARIANT_NAIVE_FOV_PCHECK_OBB: hipLaunchKernelGGL((k_render_smfr<2>), dim3(n_items), dim3(64), 0, c.stream, r); break;
 	case FR_VARIANT_MMFR_PCHECK_OBB: hipLaunchKernelGGL((k_render_mmfr<2>), dim3(n_items), dim3(64), 0, c.stream, r); break;
 	default:
-		hipLaunchKernelGGL((k_render_fov<2>), dim3(n_items), dim3(64), 0, c.stream, r);
+		if (c.keep) hipLaunchKernelGGL((k_render_fov<2, true>), dim3(n_items), dim3(64), 0, c.stream, r);
+		else hipLaunchKernelGGL((k_render_fov<2>), dim3(n_items), dim3(64), 0, c.stream, r);
 		break;
 	}
 #undef FR_LAUNCH_RENDER

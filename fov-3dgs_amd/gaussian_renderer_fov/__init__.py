@@ -56,8 +56,14 @@ def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, hig
 
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, alpha=None, gazeArray=None,
            blending=None, starter=None, ender=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None,
-           foveation=None):
+           foveation=None, appearance_only=False):
     """Render the scene for one gaze. Background tensor (bg_color) must be on the GPU.
+    appearance_only (extension, opt-in): with autograd on, the image is differentiable in the per-level appearance parameters --
+    `opacities` [P,L] and `shs_dcs` [P,L,3] (fr_backward_fov_appearance; at most 4 layers) -- so the composed model can be fine-tuned
+    through the renderer that ships it, e.g. against MetamericLoss at the frame's gaze. What the model `pc` hands over (positions,
+    scales, rotations, rest SH coefficients) is detached, as the reference's masking render detaches it
+    (gaussian_renderer/__init__.py:71-82); `highest_levels` must not require grad; packed= is refused. Without the flag (default)
+    the call is the reference's: inference-only, no gradient for anything.
     foveation (extension): a FoveationSettings -- the layer count L of the composed model (opacities [P,L], shs_dcs [P,L,3]) and
     the display geometry; None (default) = the reference's constants, exactly today's call. A model whose width does not match is
     refused.
@@ -68,7 +74,12 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
     bypass the version counter (`t.data.copy_()`, raw-pointer kernels, DLPack aliases): call invalidate_packed(pc) after
     such a write."""
     xyz = pc.get_xyz
-    if torch.is_grad_enabled():
+    if appearance_only:
+        if packed is not None:
+            raise ValueError("appearance_only: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
+        xyz = xyz.detach()
+        screenspace_points = zero_points_like(xyz)  # (no gradient of the 2D means in this mode)
+    elif torch.is_grad_enabled():
         screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
         try:
             screenspace_points.retain_grad()
@@ -107,6 +118,10 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
         scales = pc.get_scaling
         rotations = pc.get_rotation
     shs_rest = pc.get_rest_features
+    if appearance_only:
+        scales, rotations, shs_rest = scales.detach(), rotations.detach(), shs_rest.detach()
+        if opacities is None:
+            opacity = opacity.detach()  # (the model's own opacity is not the composed model's per-level tensor: pass `opacities`)
 
     if isinstance(packed, str):
         packed = _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, highest_levels, foveation)
@@ -118,7 +133,8 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
         rendered_image, radii = rasterizer(
             means3D=means3D, means2D=means2D, shs_rest=shs_rest, colors_precomp=None, opacities=opacity, scales=scales,
             rotations=rotations, cov3D_precomp=None, shs_dcs=shs_dcs, highest_levels=highest_levels,
-            gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed, foveation=foveation)
+            gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed, foveation=foveation,
+            **({"appearance_only": True} if appearance_only else {}))
     if ender is not None:
         ender.record()
 

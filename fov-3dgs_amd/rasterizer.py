@@ -382,15 +382,21 @@ def visibility_of(radii):
     return vis if vis is not None else radii > 0
 
 
-def _begin_call(lib, a, P, dev, radii, handle, fov=None):
+def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None):
     """fr_forward_begin with the visibility mask as a second output where the library has it: the mask travels as an attribute of
     `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object).
-    fov: the call's _native.Foveation (_foveation_struct), or None = today's entry points."""
+    fov: the call's _native.Foveation (_foveation_struct), or None = today's entry points.
+    keep_state: a _native.FovState = the state-keeping foveated forward (fr_forward_begin_fov_keep), which fills it at finish."""
+    if keep_state is not None and not _native.has_fov_backward(lib):
+        raise RuntimeError("fovraster: the loaded library has no foveated backward pass (fr_backward_fov_appearance): rebuild it")
     if not _native.has_forward_ext(lib):
         return lib.fr_forward_begin(C.byref(a), C.byref(handle))
     vis = torch.empty((P,), dtype=torch.bool, device=dev)  # written in full beside radii, like it
     radii._fovraster_visibility = vis
     ext = _native.ForwardExt(C.sizeof(_native.ForwardExt), vis.data_ptr())  # (read during the call only)
+    if keep_state is not None:
+        return lib.fr_forward_begin_fov_keep(C.byref(a), C.byref(ext), C.byref(fov) if fov is not None else None, C.byref(keep_state),
+                                             C.byref(handle))
     if fov is not None:
         return lib.fr_forward_begin_fov(C.byref(a), C.byref(ext), C.byref(fov), C.byref(handle))
     return lib.fr_forward_begin_ext(C.byref(a), C.byref(ext), C.byref(handle))
@@ -438,7 +444,7 @@ class FrameInFlight:
 def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                    shs_dcs=None, highest_levels=None, gaze=(0.5, 0.5), alpha=0.05, persistent=False, loss_map=None,
                    sh_rest=None, packed=None, cur_level=0.0, raw_activations=False, list_consumed=None, no_stats=False, blend_pairs=None,
-                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False):
+                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False, keep_state=None):
     """First half of a forward call on the current stream -> FrameInFlight. count (variant original only): the counting render of
     LightGaussian's global-significance pruning -- the call also returns gaussians_count (exact hits per Gaussian) and the
     important_score (fovraster.h, fr_forward_args.gaussians_count); image and radii are those of the plain call.
@@ -451,7 +457,9 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
     the argument struct made then is used again with only the gaze and the two output tensors replaced (filling it is 20 checked
     tensor arguments: 40 us of host time on a path where the host is the bottleneck). The foveation settings are part of the key
     (the caller's), and the fr_foveation struct made from them is kept beside the argument struct.
-    foveation (foveated variant): a FoveationSettings, or None = the reference's constants through the entry points without settings."""
+    foveation (foveated variant): a FoveationSettings, or None = the reference's constants through the entry points without settings.
+    keep_state (foveated variant, training): a _native.FovState with its size set -- the state-keeping forward: the frame also keeps
+    what fr_backward_fov_appearance needs and fills the struct at finish() (the caller keeps it, and the workspaces, until backward)."""
     lib = _native.load()
     _require_gpu(means3D)
     dev = means3D.device
@@ -571,9 +579,11 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if _stage_events_hook is not None:
             a.stage_events = _stage_events_hook()
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle, fov)
+        rc = _begin_call(lib, a, P, dev, radii, handle, fov, keep_state)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
+        if keep_state is not None:
+            keep.append(keep_state)  # (fr_forward_finish writes it)
     if reuse is not None:
         reuse.clear()
         if reuse_key is not None and counts is None and lease is None:  # (no per-call outputs beside the image and the radii)
@@ -921,6 +931,38 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
     return out + (dL_dsh_rest,) if dL_dsh_rest is not None else out
 
 
+def _backward_fov_native(state, bg, grad_out_color, want_colours=False, stage_events=None, blend_pairs=None, debug=False):
+    """fr_backward_fov_appearance over a kept forward state (a _native.FovState filled by the state-keeping forward, whose workspaces the
+    caller still holds) -> (dL_dopacities [P,L], dL_dshs_dcs [P,L,3], dL_dlevel_colours [P,L,3] or None), on the current stream.
+    Every tensor is written in full by the library (zero rows included)."""
+    lib = _native.load()
+    dev = grad_out_color.device
+    P, L = int(state.P), int(state.levels)
+    z = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)) if P != 0 else \
+        (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
+    if POISON_GRADIENTS and P != 0:
+        z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        g_op, g_dc = z(P, L), z(P, L, 3)
+        g_col = z(P, L, 3) if want_colours else None
+        if P != 0:
+            a = _native.BackwardFovArgs()
+            a.size, a.debug = C.sizeof(_native.BackwardFovArgs), int(bool(debug))
+            a.state = C.pointer(state)
+            bg_c, dpix = _f32_small(bg, dev), _f32(grad_out_color, dev)
+            a.background, a.dL_dpix = bg_c.data_ptr(), dpix.data_ptr()
+            a.dL_dopacities, a.dL_dshs_dcs, a.dL_dlevel_colours = g_op.data_ptr(), g_dc.data_ptr(), _ptr(g_col)
+            a.stream = torch.cuda.current_stream(dev).cuda_stream
+            if stage_events is not None:
+                a.stage_events = stage_events
+            if blend_pairs is not None:
+                a.blend_pairs = blend_pairs.data_ptr()
+            rc = lib.fr_backward_fov_appearance(C.byref(a))
+            if rc != 0:
+                raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
+    return g_op, g_dc, g_col
+
+
 def visible_rows(variant, P, geomBuffer, num_candidates):
     """The Gaussian indices (int64 [num_candidates], increasing) of the rows of a row-sparse backward call."""
     lib = _native.load()
@@ -1176,15 +1218,38 @@ def _gaze_pair(gazeArray):
 
 
 def _make_fov():
-    """Autograd function + module for the foveated (inference-only) variant."""
+    """Autograd function + module for the foveated variant: inference-only as the reference's, and with appearance_only=True
+    (extension) differentiable in the per-level appearance parameters, opacities [P,L] and shs_dcs [P,L,3]."""
     variant_id = _native.VARIANT_FOV_PCHECK_OBB
 
     class _RasterizeGaussians(torch.autograd.Function):
         @staticmethod
         def forward(ctx, means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                    raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending, packed=None, foveation=None):
+                    raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending, packed=None, foveation=None,
+                    appearance_only=False, grad_mode=True):
             args = (variant_id, raster_settings, means3D, shs_rest, colors_precomp, opacities, scales, rotations,
                     cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha))
+            # appearance_only (extension): the state-keeping forward over a leased workspace set, as the plain variants' training
+            # calls; backward is fr_backward_fov_appearance (grad_mode = torch.is_grad_enabled() at the call site)
+            ctx.keep = bool(appearance_only) and grad_mode and (ctx.needs_input_grad[4] or ctx.needs_input_grad[9])
+            if ctx.keep:
+                ctx.set_materialize_grads(False)
+                state = _native.FovState()
+                state.size = C.sizeof(_native.FovState)
+                ev = _call_events
+                if ev is not None:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                res = _forward_begin(*args, persistent=False, foveation=foveation, keep_state=state).finish()
+                if ev is not None:
+                    e1.record()
+                    ev.append(("fwd", e0, e1))
+                color, radii = res[1], res[2]
+                ctx.fov_state, ctx.ws_lease, ctx.raster_settings = state, res[-1], raster_settings
+                ctx.shapes = (tuple(opacities.shape), tuple(shs_dcs.shape))
+                ctx.save_for_backward(res[3], res[4], res[5])  # the workspaces the state points into
+                ctx.mark_non_differentiable(radii)
+                return color, radii
             if raster_settings.debug:
                 cpu_args = cpu_deep_copy_tuple(args)
                 try:
@@ -1204,11 +1269,29 @@ def _make_fov():
         def backward(ctx, grad_out_color, _):
             # RF/diff_gaussian_rasterization_fov_pcheck_obb/__init__.py:128-187: the foveated extension is
             # inference-only and hands back None for every input
-            return (None,) * 16
+            if not ctx.keep or grad_out_color is None:
+                return (None,) * 18
+            ev = _call_events
+            if ev is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            _ws = ctx.saved_tensors  # (alive until here: the state holds their addresses)
+            g_op, g_dc, _ = _backward_fov_native(ctx.fov_state, ctx.raster_settings.bg, grad_out_color,
+                                                 stage_events=_bwd_events_hook() if _bwd_events_hook is not None else None,
+                                                 debug=ctx.raster_settings.debug)
+            if ev is not None:
+                e1.record()
+                ev.append(("bwd", e0, e1))
+            grads = [None] * 18
+            if ctx.needs_input_grad[4]:
+                grads[4] = g_op.reshape(ctx.shapes[0])
+            if ctx.needs_input_grad[9]:
+                grads[9] = g_dc.reshape(ctx.shapes[1])
+            return tuple(grads)
 
     def rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending,
-                            packed=None, foveation=None):
+                            packed=None, foveation=None, appearance_only=False):
         if not torch.is_grad_enabled() and not raster_settings.debug:
             # (inference: no graph to build -- the autograd machinery around an inference-only extension is 15 us of host time a
             # frame on a path where the host sets the pace, see OVERLAP_SUCCESSIVE_FRAMES)
@@ -1218,7 +1301,7 @@ def _make_fov():
             return res[1], res[2]
         return _RasterizeGaussians.apply(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                         blending, packed, foveation)
+                                         blending, packed, foveation, appearance_only, torch.is_grad_enabled())
 
     class GaussianRasterizer(nn.Module):
         def __init__(self, raster_settings):
@@ -1231,10 +1314,18 @@ def _make_fov():
 
         def forward(self, means3D, means2D, opacities, shs_rest=None, colors_precomp=None, scales=None,
                     rotations=None, cov3D_precomp=None, shs_dcs=None, highest_levels=None, gazeArray=None,
-                    alpha=None, blending=None, packed=None, foveation=None):
+                    alpha=None, blending=None, packed=None, foveation=None, appearance_only=False):
             """foveation (extension): a FoveationSettings -- layer count and display geometry --, or None = the reference's
-            constants (4 layers, maximum pooling size 12, a display 2 wide seen from 1, blend band 0.5 / 0.5)."""
+            constants (4 layers, maximum pooling size 12, a display 2 wide seen from 1, blend band 0.5 / 0.5).
+            appearance_only (extension, opt-in): with autograd on, the image is differentiable in opacities [P,L] and shs_dcs [P,L,3]
+            (fr_backward_fov_appearance; at most 4 layers); every other input gets None, and one that requires grad is refused. Without
+            the flag the call is the reference's inference-only one."""
             raster_settings = self.raster_settings
+            if appearance_only:
+                if packed is not None:
+                    raise ValueError("appearance_only: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
+                _check_appearance_only(means3D=means3D, means2D=means2D, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
+                                       shs_rest=shs_rest, colors_precomp=colors_precomp, highest_levels=highest_levels)
             if (shs_rest is None and colors_precomp is None) or (shs_rest is not None and colors_precomp is not None):
                 raise Exception('Please provide excatly one of either SHs or precomputed colors!')
             if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -1248,7 +1339,7 @@ def _make_fov():
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                       blending, packed, foveation))
+                                       blending, packed, foveation, appearance_only))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 

@@ -377,6 +377,84 @@ int fr_backward_prefill(const fr_backward_args *args, void *fill_stream);
  * fr_backward_appearance calls over one forward state gives each call's gradients as a single call would. Never synchronises.
  * radii, means3D, scales, rotations, cov3D_precomp, opacities and the matrices are not read. */
 int fr_backward_appearance(const fr_backward_args *args);
+
+/* ---- Appearance backward pass of the FOVEATED renderer (extension; FR_VARIANT_FOV_PCHECK_OBB) ----
+ * The reference's foveated extension is inference-only (…_fov_pcheck_obb/diff_gaussian_rasterization_fov_pcheck_obb/
+ * __init__.py:128-187 returns None for every input). Here the per-level APPEARANCE parameters of the composed model -- opacities
+ * [P,L] and shs_dcs [P,L,3], what the mask-learning loop learns and all that masking=True differentiates
+ * (gaussian_renderer/__init__.py:71-82) -- get a gradient through the renderer that consumes them. The arithmetic is the
+ * reference's RS / R0 backward (cuda_rasterizer/backward.cu:399-557, restricted as fr_backward_appearance restricts it) applied to
+ * the forward pass of …_fov_pcheck_obb/cuda_rasterizer/forward.cu:262-609:
+ *   single-level tile, level l = int(tile_min): pixel = C_l + T_l bg; Gaussian g takes part with opacities[g][l] and
+ *     colour[g][l] = max(0, SH_C0 shs_dcs[g][l] + rest SH + 0.5);
+ *   two-level tile (l1, l2 = l1 + 1): pixel = w1 (C_1 + T_1 bg) + (1 - w1)(C_2 + T_2 bg) (forward.cu:455-470); w1 depends on the
+ *     tile's geometry and the settings only, so state 1 receives w1 dL/dpixel and state 2 (1 - w1) dL/dpixel; state 1 of a pixel
+ *     with est > l2 starts finished (T = 1, no contributor); state 2 skips every Gaussian with highest_level + 1 < tile_min + 1
+ *     (forward.cu:399);
+ *   per blended (pixel, state, Gaussian) pair: dL/dcolour[g][l] += alpha T dL/dpix, dL/dalpha from the colour behind the entry and
+ *     the background term, dL/dopacities[g][l] += G dL/dalpha; the saturation alpha = min(0.99, o G) is not differentiated
+ *     (backward.cu:497-541).
+ *
+ * fr_forward_begin_fov_keep / fr_forward_fov_keep_call: fr_forward_begin_fov / fr_forward_fov_call that also KEEP what the backward
+ * pass needs. Image and radii are those of the plain call bit for bit (the same blend; a second instantiation of the blend kernel
+ * that also stores, per pixel and level state, the transmittance the state ended with and the list position of its last
+ * contributor -- final_T / n_contrib of forward.cu:267-384 per state). The resize callbacks are asked for LARGER geometry and image
+ * workspaces, fr_geometry_bytes_fov_keep / fr_image_bytes_fov_keep: the plain call's layout with, behind it, one 64-byte row of
+ * gradient sums per Gaussian resp. two planes of each of the two per-state arrays; fr_geometry_bytes_fov / fr_image_bytes and every
+ * introspection pointer answer what they answered. `state` (size = sizeof(fr_fov_state) as the caller was compiled) is filled by
+ * fr_forward_finish (by the call itself with fr_forward_fov_keep_call) and must stay where it is until then; it is valid for as
+ * long as the three workspaces are left alone.
+ * Refused with FR_ERR_INVALID before anything is enqueued, the message names the field: a variant other than
+ * FR_VARIANT_FOV_PCHECK_OBB; fr_foveation.levels > 4 (levels 5 .. 8 would need a second row of sums per Gaussian); a packed model
+ * (packed_geom / packed_colour / packed_cull: training renders from the ordinary tensors); state NULL or its size too small. */
+typedef struct fr_fov_state {
+	uint32_t size;                  /* in: sizeof(fr_fov_state) */
+	int32_t variant;                /* out, all below: FR_VARIANT_FOV_PCHECK_OBB */
+	int32_t P, W, H;
+	int32_t levels;                 /* fr_foveation.levels (4 without settings) */
+	int32_t num_rendered;           /* fr_forward_args.num_rendered */
+	int32_t num_items;              /* blend work items of the frame (tile << 3 | band | level state << 1 | two-level << 2) */
+	float start_blend, blend_width; /* fr_foveation */
+	char *geometry, *binning, *image; /* the workspaces the resize callbacks returned */
+} fr_fov_state;
+int fr_forward_begin_fov_keep(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state, fr_frame **frame);
+int fr_forward_fov_keep_call(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state);
+size_t fr_geometry_bytes_fov_keep(int32_t P, int32_t levels);
+size_t fr_image_bytes_fov_keep(int32_t W, int32_t H);
+/* introspection (tests): the kept per-state planes, [2][W*H] each: plane 0 = the state of a single-level tile / state 1 of a
+ * two-level tile, plane 1 = state 2 (written in two-level tiles only) */
+const float *fr_image_fov_state_T(int32_t W, int32_t H, const char *image);
+const uint32_t *fr_image_fov_state_n(int32_t W, int32_t H, const char *image);
+/* fr_backward_fov_appearance: the gradients over a kept forward state. size = sizeof(fr_backward_fov_args).
+ *   state               the forward call's, unchanged
+ *   background [3], dL_dpix [3,H,W]   required (background: what the forward call blended with)
+ *   dL_dopacities       [P,L], required
+ *   dL_dshs_dcs         [P,L,3], required: SH_C0 dL/dcolour[g][l], zero for a channel the forward pass clamped at that level
+ *                       (backward.cu:20-139; a pre-clamp value of exactly 0 counts as clamped)
+ *   dL_dlevel_colours   [P,L,3] or NULL: dL/dcolour[g][l]
+ *   stage_events        optional [3]: recorded on `stream` in front of the tile pass, between the two passes and behind them
+ *   blend_pairs         optional [T] diagnostic as fr_backward_args.blend_pairs
+ * L = state->levels: the outputs have the model's own width. Every output is written in full: rows of Gaussians outside the
+ * frame's visible list, of Gaussians that landed in no tile, and levels no tile used are exact zeros. A tile pass over the forward's
+ * work items (longest list first; a few lanes' float atomics into one or two 64-byte rows per entry pair, as fr_backward_appearance's)
+ * and a per-Gaussian pass that clears the sums it read: a second call over the same state gives the same gradients. Never
+ * synchronises. FR_ERR_INVALID before anything is enqueued, naming the field: state NULL / of another variant / with levels > 4, a
+ * required pointer NULL. */
+typedef struct fr_backward_fov_args {
+	uint32_t size;
+	int32_t debug;
+	const fr_fov_state *state;
+	const float *background;
+	const float *dL_dpix;
+	float *dL_dopacities;
+	float *dL_dshs_dcs;
+	float *dL_dlevel_colours;
+	void *stream;
+	void **stage_events;
+	uint32_t *blend_pairs;
+} fr_backward_fov_args;
+int fr_backward_fov_appearance(const fr_backward_fov_args *args);
+
 int fr_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, const float *projmatrix,
 	uint8_t *present /* [P] bool */, void *stream);
 
