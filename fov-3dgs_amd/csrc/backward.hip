@@ -161,8 +161,8 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 		tlf = a.tile_lv[a.T + tile];                                  // tile_min
 		tgx = a.tile_lv[2 * (size_t)a.T + tile]; tgy = a.tile_lv[3 * (size_t)a.T + tile];
 		L2f = tlf + 1.0f;
-		lev = f2i(tlf) + (upper ? 1 : 0);
-		if (lev < 0 || lev >= FR_FOV_LEVELS) return;                  // (four level rows, four quarters of the row of sums)
+		lev = max(f2i(tlf) + (upper ? 1 : 0), 0);                     // (tile_min <= -1: level 0, as k_render_fov reads it)
+		if (lev >= FR_FOV_LEVELS) return;                              // (four level rows, four quarters of the row of sums)
 	}
 	const size_t state_plane = (FOV && upper) ? plane : 0;
 
@@ -189,13 +189,17 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 		{
 			if (two_level)
 			{
-				// the state's share of the pixel, as k_render_fov forms it (RF forward.cu:455-470): w1 = 1 - smoothstep
+				// the state's share of the pixel (RF forward.cu:455-470): w1 = 1 - smoothstep(x), 1 - w1 = smoothstep(x). Formed here
+				// as the factored polynomials (1 - x)^2 (1 + 2 x) and x^2 (3 - 2 x): the forward's 1 - (3 x^2 - 2 x^3) cancels where x
+				// is near 1 and rounds to a multiple of 6e-8 -- harmless in a pixel's colour, but a RELATIVE error of 1e-4 .. 1e-3 in
+				// a share of 1e-3 .. 1e-4, and a row that meets the lower state only at such pixels carries it whole. So the pass is
+				// the derivative of the blend as written, not of the forward's rounded weight; what is left is the rounding of est
+				// itself (2 ulp(est) / (1 - x) relative), which the forward shares (tests/fov_backward_scenes.py).
 				const float est = tlf + ((float)lx * tgx + (float)tile_row<PPL>(tid, k) * tgy) / (float)FR_TILE;
 				float x = fabsf(est - ((float)f2i(tlf) + a.start_blend)) / a.blend_width;
 				x = fmaxf(0.0f, fminf(1.0f, x));
-				const float bT = 3 * x * x - 2 * x * x * x;
-				const float w1 = 1 - bT;
-				const float w = upper ? (1.f - w1) : w1;
+				const float omx = 1.0f - x;
+				const float w = upper ? x * x * (3.0f - 2.0f * x) : omx * omx * (1.0f + 2.0f * x);
 				dp0[k] *= w; dp1[k] *= w; dp2[k] *= w;
 			}
 		}

@@ -593,7 +593,9 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 		float4 p0 = make_float4(0, 0, 0, 0), pl1 = p0;
 		float2 p1 = make_float2(0, 0);
 		// this wave's level row of every item (wave-uniform: a scalar base address)
-		const int lev = upper ? L2 : L1;
+		// (a tile_min <= -1 -- a frame of a tile or two, whose tile centres lie outside it -- gives L1 = -1, where the reference
+		// indexes the previous Gaussian's level 3; such a tile never blends, and k_bin evaluated its level-0 rows: level 0)
+		const int lev = max(upper ? L2 : L1, 0);
 		const float4 *const lvrow = lev >= FR_FOV_LEVELS ? a.lvl_hi + (lev - FR_FOV_LEVELS) : a.lvl + lev;
 		auto fetch = [&](int e)
 		{

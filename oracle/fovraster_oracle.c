@@ -180,6 +180,8 @@ static int f2i(real v)
 }
 static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
+/* the level a tile indexes the per-level arrays with: int(tile_min), negative -> 0 (see walk_one) */
+#define ORC_LEVEL_INDEX(i) imax((i), 0)
 
 /* ---- tiny glm-like column-major mat3: m.c[col][row]; product order as glm ---- */
 typedef struct { real c[3][3]; } m3;
@@ -632,9 +634,13 @@ static int64_t walk_one(const orc_in *in, orc_out *o, int idx, int gx, int gy, i
 	if (cull && count == 0) o->radii[idx] = 0;
 	else if (fov)
 	{
-		/* RF rasterizer_impl.cu:374-381 */
-		o->level_ranges[2 * idx] = f2i(lowest);
-		int hi = f2i(highest);
+		/* RF rasterizer_impl.cu:374-381. A tile whose tile_min is <= -1 (a level gradient of two levels per tile: frames of a
+		 * tile or two, whose tile centres lie outside the frame) gives int(tile_min) = -1 there, and the reference then indexes
+		 * shs_dcs / fov_colors / opacities at level -1: the previous Gaussian's level 3, outside the arrays for Gaussian 0 --
+		 * undefined behaviour (this file wrote 12 bytes in front of fov_colors). Defined here as the HIP library defines it:
+		 * a negative level is level 0 (ORC_LEVEL_INDEX). */
+		o->level_ranges[2 * idx] = ORC_LEVEL_INDEX(f2i(lowest));
+		int hi = ORC_LEVEL_INDEX(f2i(highest));
 		if (be_blend) hi = imin(hi + 1, FOV_NUM - 1);
 		o->level_ranges[2 * idx + 1] = hi;
 	}
@@ -847,7 +853,7 @@ static void render_fov(const orc_in *in, orc_out *o)
 			const uint32_t cur = (uint32_t)(tx + twn * ty);
 			const int blending = o->tile_blend[cur];
 			const real tlf = o->tile_min[cur];
-			const int tli = f2i(tlf);
+			const int tli = ORC_LEVEL_INDEX(f2i(tlf)); /* (a tile with tile_min <= -1 never blends: the index is its only use) */
 			for (int ly = 0; ly < BLOCK_Y; ly++)
 				for (int lx = 0; lx < BLOCK_X; lx++)
 				{

@@ -12,7 +12,9 @@ forward pass. This file is a restatement of tests/numpy_fov_rasterizer.blend_fov
   * VALUES AND GRADIENTS in the dtype asked for (float64: the reference; float32: the same arithmetic for checks.check_against_noise)
     with the decisions FROZEN. Per state and pixel, entries j in list order with alpha_j = min(0.99, o_j G_j) where blended, else 0:
         T_j = prod_{i<j} (1 - alpha_i),  w_j = alpha_j T_j,  value = sum_j w_j c_j + T_end bg
-        dL/dc_j      += w_j dL                                       (dL = the state's share of dL/dpixel: w1 or 1 - w1 or 1)
+        dL/dc_j      += w_j dL                                       (dL = the state's share of dL/dpixel: w1 or 1 - w1 or 1; w1 is
+                                                                      a value like the others: in float32, or from the same fp32 `est`
+                                                                      in double)
         dL/dalpha_j   = T_j (c_j . dL) - (sum_{i>j} w_i (c_i . dL) + T_end (bg . dL)) / (1 - alpha_j)
         dL/do_j      += G_j dL/dalpha_j                              (the min is not differentiated: backward.cu:497-541)
     and dL/dshs_dcs = SH_C0 dL/dcolour where the level colour is > 0, else 0 (clamped at that level).
@@ -69,12 +71,20 @@ class FovBackwardRef:
                     x = np.abs(est - (f32(L1) + f32(start_blend))) / f32(blend_width)
                     x = np.fmax(f32(0), np.fmin(f32(1), x))
                     w1 = f32(1) - (f32(3) * x * x - f32(2) * x * x * x)
+                    # the same weight in double, from the tile map's fp32 numbers (tile_min, the gradient, the fp32 constants):
+                    # w1 = 1 - smoothstep cancels where x is near 1 (w1 ~ 3 (1 - x)^2), so the fp32 rounding of est (2e-7) and of w1
+                    # (6e-8 absolute) is a RELATIVE error of up to 1e-4 in the lower state's share of a pixel -- part of the fp32
+                    # arithmetic's noise, not a decision to freeze (the decision est > L2 above stays the fp32 one)
+                    est64 = np.float64(tmin[t]) + (lx * np.float64(tgx[t]) + ly * np.float64(tgy[t])) / BLOCK
+                    x64 = np.abs(est64 - (np.float64(L1) + np.float64(f32(start_blend)))) / np.float64(f32(blend_width))
+                    x64 = np.fmax(0.0, np.fmin(1.0, x64))
+                    w1d = 1.0 - (3.0 * x64 * x64 - 2.0 * x64 * x64 * x64)
                 exists = ~((highest[g] + f32(1)) < (tmin[t] + f32(1)))
-                specs = [(L1, ~inside | (est > f32(L1 + 1)), w1, None), (L1 + 1, ~inside, f32(1) - w1, exists)]
+                specs = [(L1, ~inside | (est > f32(L1 + 1)), (w1, w1d), None), (L1 + 1, ~inside, (f32(1) - w1, 1.0 - w1d), exists)]
             else:
-                specs = [(L1, ~inside, np.ones(256, f32), None)]
-            for lev, done0, wgt, exists in specs:
-                lev = min(lev, self.L - 1)
+                specs = [(L1, ~inside, (np.ones(256, f32), np.ones(256)), None)]
+            for lev, done0, (wgt, wgt_d), exists in specs:
+                lev = max(min(lev, self.L - 1), 0)   # (tile_min <= -1: level 0, as the oracle and the library index it)
                 with np.errstate(all="ignore"):
                     a = np.fmin(f32(0.99), self.opac[g, lev][:, None] * e32)
                     cand = support & ~(a < f32(1) / f32(255))
@@ -96,7 +106,8 @@ class FovBackwardRef:
                     done |= stop
                     acc[j] = ac
                     last[ac] = j + 1
-                states.append(dict(lev=lev, acc=acc, wgt=np.where(inside, wgt, 0).astype(np.float64), final_T=T, n_contrib=last))
+                states.append(dict(lev=lev, acc=acc, wgt32=np.where(inside, wgt, 0).astype(f32), wgt=np.where(inside, wgt_d, 0).astype(np.float64),
+                                   final_T=T, n_contrib=last))
             self.tiles.append(dict(g=g, X=X, Y=Y, inside=inside, blend=blend, states=states, dx=dx, dy=dy, conic=conic[g]))
         # which levels of which Gaussians a tile of each kind used (for the tests' sampling): [P, L] bools
         self.used_single, self.used_blend = np.zeros((self.P, self.L), bool), np.zeros((self.P, self.L), bool)
@@ -121,6 +132,10 @@ class FovBackwardRef:
         Tfin = Tafter[-1] if len(alpha) else np.ones(256, F)
         return alpha, om, Tbefore, Tfin
 
+    def _wgt(self, st, F):
+        """the state's share of its pixels: float32 as the forward pass forms it, or the same expression in double"""
+        return st["wgt32"] if F is np.float32 else st["wgt"].astype(F)
+
     def _colours(self, colours, F):
         return np.nan_to_num(np.asarray(colours, F), nan=0.0)
 
@@ -139,7 +154,7 @@ class FovBackwardRef:
             for st in tl["states"]:
                 alpha, om, Tb, Tfin = self._state(tl, st, G, opac, F)
                 c = col[tl["g"], st["lev"]]
-                val += st["wgt"].astype(F)[:, None] * ((alpha * Tb).T @ c + Tfin[:, None] * bg[None, :])
+                val += self._wgt(st, F)[:, None] * ((alpha * Tb).T @ c + Tfin[:, None] * bg[None, :])
             if pixels:
                 out[t] = val
             else:
@@ -182,7 +197,7 @@ class FovBackwardRef:
                 if not st["acc"].any():
                     continue
                 alpha, om, Tb, Tfin = self._state(tl, st, G, opac, F)
-                dlw = dl * st["wgt"].astype(F)[:, None]
+                dlw = dl * self._wgt(st, F)[:, None]
                 c = col[g, st["lev"]]
                 w = alpha * Tb
                 cd = c @ dlw.T                                              # c_j . dL per pixel

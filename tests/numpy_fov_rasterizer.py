@@ -497,13 +497,13 @@ def blend_fov(ar, pr, cam, lv, point_list, ranges, opac4, colours, highest):
             go = ~done[ti] & ~((power > 0) | (power < lit(-4.5)))
             e = _exp(ar, power)
             # level 1 (the only level of a single-level tile)
-            a1 = np.fmin(lit(0.99), opac4[g, np.minimum(L1[ti], FOV_NUM - 1)][:, None] * e)
+            a1 = np.fmin(lit(0.99), opac4[g, np.clip(L1[ti], 0, FOV_NUM - 1)][:, None] * e)
             go1 = go & ~L1_done[ti] & ~(a1 < F(1) / F(255))
             t1 = T1[ti] * (F(1) - a1)
             stop1 = go1 & (t1 < lit(0.0001))
             acc1 = go1 & ~stop1
             w1 = a1 * T1[ti]
-            f1 = colours[g, np.minimum(L1[ti], FOV_NUM - 1)][:, None, :]
+            f1 = colours[g, np.clip(L1[ti], 0, FOV_NUM - 1)][:, None, :]
             C1[ti] = np.where(acc1[..., None], C1[ti] + f1 * w1[..., None], C1[ti])
             T1[ti] = np.where(acc1, t1, T1[ti])
             L1_done[ti] |= stop1
@@ -573,8 +573,10 @@ def rasterize(variant, scene, cam, dtype=np.float32):
         hi[g[single_kept]] = tmin[tile[single_kept]]                # one-tile rect: highest_level_used = level, no max with 0
         seen = count > 0
         lr = np.zeros((P, 2), np.int32)
-        lr[seen, 0] = np.trunc(lo[seen]).astype(np.int32)
-        hi_i = np.trunc(hi).astype(np.int32)
+        # (a tile_min <= -1 -- frames of a tile or two -- makes the reference index level -1, outside its arrays: level 0 here, as in the
+        # oracle and the HIP library; such a tile never blends, so the index is the level's only use)
+        lr[seen, 0] = np.maximum(np.trunc(lo[seen]).astype(np.int32), 0)
+        hi_i = np.maximum(np.trunc(hi).astype(np.int32), 0)
         hi_i = np.where(anyb, np.minimum(hi_i + 1, FOV_NUM - 1), hi_i)
         lr[seen, 1] = hi_i[seen]
         point_list, ranges, keys = sort_instances(pr, g, tile, kept, T)

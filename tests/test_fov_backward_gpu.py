@@ -38,9 +38,10 @@ def _tensors(scene):
     return {k: _t(scene.get(k), DEV) for k in ("means3D", "shs", "opacities", "scales", "rotations", "shs_dcs", "highest_levels")}
 
 
-def keep_forward(scene, cam, settings=None):
+def keep_forward(scene, cam, settings=None, allow_empty=False):
     """The state-keeping forward by direct call -> dict: image and radii (device tensors), the tile lists as Gaussian indices, the
-    kept per-state planes, and the state for backward(). The dict holds the workspace lease."""
+    kept per-state planes, and the state for backward(). The dict holds the workspace lease.
+    allow_empty: the frame may render no instance at all (then it has no work items and an empty point list)."""
     lib = _native.load()
     rs = settings_from(cam, DEV, debug=True)
     t = _tensors(scene)
@@ -54,16 +55,22 @@ def keep_forward(scene, cam, settings=None):
     W, H, P = rs.image_width, rs.image_height, t["means3D"].shape[0]
     T = ((W + 15) // 16) * ((H + 15) // 16)
     assert (state.variant, state.P, state.W, state.H, state.num_rendered) == (VID, P, W, H, num_rendered)
-    assert state.levels == (4 if settings is None else settings.levels) and 0 < state.num_items <= 4 * T
+    assert state.levels == (4 if settings is None else settings.levels)
+    assert 0 < state.num_items <= 4 * T or (allow_empty and num_rendered == 0 and 0 <= state.num_items <= 4 * T)
     assert state.geometry == geom.data_ptr() and state.image == img.data_ptr() and state.binning == binb.data_ptr()
     assert geom.numel() >= lib.fr_geometry_bytes_fov_keep(P, state.levels) and img.numel() >= lib.fr_image_bytes_fov_keep(W, H)
     out = dict(color=color, radii=radii, state=state, rs=rs, tensors=t, lease=res[-1], buffers=(geom, binb, img), num_rendered=num_rendered)
     out["ranges"] = _view(img, lib.fr_image_ranges(VID, W, H, img.data_ptr()), 2 * T, torch.int32).cpu().numpy().astype(np.uint32).reshape(T, 2)
     vis = vis_list_of(lib, VID, P, geom)
-    items = _view(binb, lib.fr_binning_point_list(VID, num_rendered, binb.data_ptr()), num_rendered, torch.int32).long()
-    out["point_list"] = vis[items].cpu().numpy().astype(np.uint32)
+    if num_rendered > 0:
+        items = _view(binb, lib.fr_binning_point_list(VID, num_rendered, binb.data_ptr()), num_rendered, torch.int32).long()
+        out["point_list"] = vis[items].cpu().numpy().astype(np.uint32)
+    else:
+        out["point_list"] = np.zeros(0, np.uint32)
     out["final_T"] = _view(img, lib.fr_image_fov_state_T(W, H, img.data_ptr()), 2 * W * H, torch.float32).cpu().numpy().reshape(2, H, W)
     out["n_contrib"] = _view(img, lib.fr_image_fov_state_n(W, H, img.data_ptr()), 2 * W * H, torch.int32).cpu().numpy().reshape(2, H, W)
+    tl = _view(img, lib.fr_image_tile_levels(W, H, img.data_ptr()), 5 * T, torch.float32).cpu().numpy().reshape(5, T)   # the library's level map
+    out["tile_min"], out["tile_gx"], out["tile_gy"], out["tile_blend"] = tl[1], tl[2], tl[3], (tl[4] != 0).astype(np.uint8)
     lv = _view(geom, lib.fr_geometry_level_colours(P, geom.data_ptr()), 16 * P, torch.float32).view(P, 4, 4).cpu().numpy()
     rows = np.full((P, 4, 4), np.nan, np.float32)
     rows[vis.cpu().numpy()] = lv[:len(vis)]
@@ -302,3 +309,140 @@ def test_fine_tuning_the_opacities_through_the_foveated_renderer():
     torch.cuda.synchronize()
     for g in (opac.grad, dcs.grad):
         assert torch.isfinite(g).all() and (g != 0).sum() >= MAIN_ROWS
+
+
+# ---- 10. - 14. the host side of the autograd path, on the faint scene ------------------------------------------------------------
+# tests/fov_backward_scenes.py's `faint` (opacities x 0.1: 3034 live rows at gaze (0.4, 0.55), 1305 at (0.2, 0.35)) through
+# gaussian_renderer_fov.render(..., appearance_only=True). Gradients of one graph are compared with those of the same graph run alone
+# by check_grad (float atomics move the last bits from run to run) with min_rows = the scenes' MIN_LIVE.
+FAINT_A, FAINT_B = dict(alpha=0.6, gaze=(0.4, 0.55)), dict(alpha=0.6, gaze=(0.2, 0.35))
+from tests.backward_scenes import MIN_LIVE  # noqa: E402  (the scenes' condition: live rows of every large scene)
+_alone_cache = {}
+
+
+def _faint_model(settings=None):
+    from tests.fov_backward_scenes import OPACITY_FACTOR
+    cloud = small_cloud(3000, 3)
+    L = 4 if settings is None else int(settings.levels)
+    highest, dcs, opac = syn.foveation_layers(cloud, seed=4, **({} if settings is None else {"fractions": (1.0 / L,) * L}))
+    return cloud.to(DEV), small_camera().to(DEV), torch.tensor(R.BG, device=DEV), highest.to(DEV), dcs.to(DEV), (opac * OPACITY_FACTOR).to(DEV)
+
+
+def _faint_dL():
+    return torch.tensor(R.dL_for(dict(image_height=120, image_width=200)), device=DEV)
+
+
+def _graph(model, kw, **extra):
+    """forward of one autograd graph -> (render dict, opacities leaf, shs_dcs leaf)"""
+    cloud, cam, bg, highest, dcs, opac = model
+    o, d = opac.clone().requires_grad_(True), dcs.clone().requires_grad_(True)
+    return _render(cloud, cam, bg, highest, d, o, kw, appearance_only=True, **extra), o, d
+
+
+def _finish(graph, dL):
+    out, o, d = graph
+    (out["render"] * dL).sum().backward()
+    torch.cuda.synchronize()
+    assert o.grad.shape == o.shape and d.grad.shape == d.shape
+    return o.grad.cpu().numpy(), d.grad.cpu().numpy()
+
+
+def _alone(which):
+    """the gradients of graph A / B of the faint scene run alone (once per session)"""
+    if which not in _alone_cache:
+        _alone_cache[which] = _finish(_graph(_faint_model(), FAINT_A if which == "A" else FAINT_B), _faint_dL())
+    return _alone_cache[which]
+
+
+def _same(got, want, tag, L=4):
+    for g, w, k in zip(got, want, ("opacities", "shs_dcs")):
+        assert np.isfinite(g).all()
+        check_grad(R.rows(g, L), R.rows(w, L), f"{tag} {k}", min_rows=MIN_LIVE)
+
+
+def _workspaces(out):
+    """addresses of the workspace buffers the graph of a render holds for its backward pass"""
+    saved = out["render"].grad_fn.saved_tensors
+    assert len(saved) == 3
+    return {t.data_ptr() for t in saved}
+
+
+def test_two_graphs_alive_at_once_keep_their_own_state():
+    """forward A (gaze (0.4, 0.55)), forward B (gaze (0.2, 0.35)), backward B, backward A: each graph's gradients are those of the same
+    graph run alone, and the two graphs held different workspace sets (a set shared between them would hand A's backward B's lists,
+    level table and state planes)."""
+    _need_gpu()
+    model, dL = _faint_model(), _faint_dL()
+    a = _graph(model, FAINT_A)
+    b = _graph(model, FAINT_B)
+    assert not (_workspaces(a[0]) & _workspaces(b[0])), "two live graphs share a workspace buffer"
+    got_b = _finish(b, dL)
+    got_a = _finish(a, dL)
+    _same(got_b, _alone("B"), "B beside A")
+    _same(got_a, _alone("A"), "A after B")
+    assert not np.array_equal(got_a[0], got_b[0])
+
+
+def test_a_graph_dropped_without_backward_leaves_the_next_one_intact():
+    _need_gpu()
+    import gc
+    model, dL = _faint_model(), _faint_dL()
+    dropped = _graph(model, FAINT_A)
+    del dropped
+    gc.collect()
+    _same(_finish(_graph(model, FAINT_B), dL), _alone("B"), "after a dropped graph")
+    kept = _graph(model, FAINT_A)   # ... and one dropped while another is alive
+    dropped = _graph(model, FAINT_B)
+    del dropped
+    gc.collect()
+    _same(_finish(kept, dL), _alone("A"), "beside a dropped graph")
+
+
+def test_forward_and_backward_on_a_non_default_stream():
+    _need_gpu()
+    want = _alone("A")
+    model, dL = _faint_model(), _faint_dL()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream(device=DEV)
+    s.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(s):
+        graph = _graph(model, FAINT_A)
+        (graph[0]["render"] * dL).sum().backward()
+    torch.cuda.current_stream(DEV).wait_stream(s)
+    torch.cuda.synchronize()
+    _same((graph[1].grad.cpu().numpy(), graph[2].grad.cpu().numpy()), want, "side stream")
+    with torch.no_grad():   # the image on that stream is the default stream's
+        cloud, cam, bg, highest, dcs, opac = model
+        plain = _render(cloud, cam, bg, highest, dcs, opac, FAINT_A)["render"]
+    torch.cuda.synchronize()
+    assert torch.equal(plain, graph[0]["render"].detach())
+
+
+@pytest.mark.parametrize("name", tuple(SETTINGS))
+def test_two_and_three_levels_through_autograd(name):
+    """render(..., foveation=settings, appearance_only=True) on fov_backward_scenes' faint-L2 / faint-L3: the gradients have the
+    model's shapes [P,L] / [P,L,3] and equal the direct call's."""
+    _need_gpu()
+    from tests import fov_backward_scenes as fs
+    settings, alpha, gaze = SETTINGS[name]
+    L = settings.levels
+    r = fs.reference(f"faint-{name}")
+    dL = R.dL_for(r["cam"])
+    direct = backward(keep_forward(r["scene"], r["cam"], settings), dL, want_colours=False)
+    model = _faint_model(settings)
+    np.testing.assert_allclose(model[5].cpu().numpy(), r["scene"]["opacities"], rtol=1e-6)   # (the scene of the direct call)
+    got = _finish(_graph(model, dict(alpha=alpha, gaze=gaze), foveation=settings), torch.tensor(dL, device=DEV))
+    assert got[0].shape == (3000, L) and got[1].shape == (3000, L, 3)
+    _same(got, (direct["dL_dopacities"], direct["dL_dshs_dcs"]), f"{name} autograd vs direct", L)
+
+
+def test_a_non_contiguous_upstream_gradient():
+    """dL/dimage handed to backward as a [W,H,3] tensor permuted to [3,H,W] gives the contiguous tensor's gradients."""
+    _need_gpu()
+    model, dL = _faint_model(), _faint_dL()
+    strided = dL.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    assert strided.shape == dL.shape and not strided.is_contiguous() and torch.equal(strided, dL)
+    out, o, d = _graph(model, FAINT_A)
+    out["render"].backward(gradient=strided)
+    torch.cuda.synchronize()
+    _same((o.grad.cpu().numpy(), d.grad.cpu().numpy()), _alone("A"), "strided dL")
