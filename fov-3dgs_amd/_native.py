@@ -78,6 +78,19 @@ class BackwardFovArgs(C.Structure):
                 ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p)), ("blend_pairs", _FP)]
 
 
+class BackwardFovFullArgs(C.Structure):
+    """fr_backward_fov_full_args"""
+    _fields_ = [("size", C.c_uint32), ("debug", C.c_int32), ("state", C.POINTER(FovState)),
+                ("P", C.c_int32), ("M", C.c_int32), ("sh_degree", C.c_int32),
+                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
+                ("means3D", _FP), ("scales", _FP), ("rotations", _FP), ("shs_rest", _FP),
+                ("viewmatrix", _FP), ("projmatrix", _FP), ("campos", _FP), ("background", _FP), ("dL_dpix", _FP),
+                ("dL_dopacities", _FP), ("dL_dshs_dcs", _FP), ("dL_dlevel_colours", _FP),
+                ("dL_dshs_rest", _FP), ("dL_dmeans3D", _FP), ("dL_dscales", _FP), ("dL_drotations", _FP), ("dL_dmeans2D", _FP),
+                ("dL_dconic", _FP),
+                ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p)), ("blend_pairs", _FP)]
+
+
 class BackwardArgs(C.Structure):
     _fields_ = [
         ("variant", C.c_int32), ("P", C.c_int32), ("D", C.c_int32), ("M", C.c_int32), ("R", C.c_int32),
@@ -177,7 +190,8 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance",
            "fr_vq_workspace_bytes", "fr_vq_nearest", "fr_vq_gather", "fr_vq_update", "fr_vq_replace", "fr_pack_bits", "fr_unpack_bits",
            "fr_forward_begin_fov_keep", "fr_forward_fov_keep_call", "fr_geometry_bytes_fov_keep", "fr_image_bytes_fov_keep",
-           "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance")
+           "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance",
+           "fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -186,7 +200,10 @@ FOVEATION_EXPORTS = ("fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry
 # ... and the foveated renderer's appearance backward pass: has_fov_backward(); without it appearance_only on that renderer raises
 FOV_BACKWARD_EXPORTS = ("fr_forward_begin_fov_keep", "fr_forward_fov_keep_call", "fr_geometry_bytes_fov_keep", "fr_image_bytes_fov_keep",
                         "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance")
-OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS + FOV_BACKWARD_EXPORTS
+# ... and its full backward pass (geometry, rest SH): has_fov_full_backward(); without it differentiable=True on that renderer raises
+FOV_FULL_BACKWARD_EXPORTS = ("fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov")
+OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS + FOV_BACKWARD_EXPORTS + FOV_FULL_BACKWARD_EXPORTS
+FOV_STATE_FULL = 0x100  # FR_FOV_STATE_FULL: set in fr_fov_state.variant by the _full forward
 
 _lib = None
 
@@ -318,6 +335,15 @@ def load():
             getattr(lib, n).restype = C.c_void_p
         lib.fr_backward_fov_appearance.argtypes = [C.POINTER(BackwardFovArgs)]
         lib.fr_backward_fov_appearance.restype = C.c_int
+    if has_fov_full_backward(lib):
+        lib.fr_forward_begin_fov_keep_full.argtypes = lib.fr_forward_begin_fov_keep.argtypes
+        lib.fr_forward_begin_fov_keep_full.restype = C.c_int
+        lib.fr_forward_fov_keep_full_call.argtypes = lib.fr_forward_fov_keep_call.argtypes
+        lib.fr_forward_fov_keep_full_call.restype = C.c_int
+        lib.fr_geometry_bytes_fov_keep_full.argtypes = [C.c_int32, C.c_int32]
+        lib.fr_geometry_bytes_fov_keep_full.restype = C.c_size_t
+        lib.fr_backward_fov.argtypes = [C.POINTER(BackwardFovFullArgs)]
+        lib.fr_backward_fov.restype = C.c_int
     lib.fr_forward_finish.argtypes = [C.c_void_p]
     lib.fr_forward_finish.restype = C.c_int
     lib.fr_backward_prefill.argtypes = [C.POINTER(BackwardArgs), C.c_void_p]
@@ -407,6 +433,12 @@ def has_fov_backward(lib=None):
     """the loaded library has the foveated renderer's appearance backward pass (fr_backward_fov_appearance)"""
     lib = load() if lib is None else lib
     return all(hasattr(lib, n) for n in FOV_BACKWARD_EXPORTS)
+
+
+def has_fov_full_backward(lib=None):
+    """the loaded library has the foveated renderer's full backward pass (fr_backward_fov)"""
+    lib = load() if lib is None else lib
+    return has_fov_backward(lib) and all(hasattr(lib, n) for n in FOV_FULL_BACKWARD_EXPORTS)
 
 
 def last_error():

@@ -282,7 +282,8 @@ static int validate_fov_keep(const fr_forward_args *a, const fr_foveation *fov, 
 	return FR_OK;
 }
 
-static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, bool keep, fr_frame **out)
+// keep: 0 = the inference frame, 1 = the state-keeping forward, 2 = the same for the full backward pass (fr_forward_begin_fov_keep_full)
+static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, int keep, fr_frame **out)
 {
 	if (!out) { set_error("null frame handle"); return FR_ERR_INVALID; }
 	*out = nullptr;
@@ -310,7 +311,7 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	{
 		const uint32_t sz = keep_state->size;
 		memset(keep_state, 0, sizeof(fr_fov_state));
-		keep_state->size = sz; keep_state->variant = a->variant; keep_state->P = a->P; keep_state->W = a->W; keep_state->H = a->H;
+		keep_state->size = sz; keep_state->variant = a->variant | (keep == 2 ? FR_FOV_STATE_FULL : 0); keep_state->P = a->P; keep_state->W = a->W; keep_state->H = a->H;
 		keep_state->levels = c.fov.levels; keep_state->start_blend = c.fov.start_blend; keep_state->blend_width = c.fov.blend_width;
 	}
 	if (a->P == 0)
@@ -327,8 +328,8 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	c.focal_y = a->H / (2.0f * a->tanfovy);
 	c.focal_x = a->W / (2.0f * a->tanfovx);
 
-	char *gptr = a->geometry_resize(a->resize_user[0], keep ? carve_fov_keep_geom((size_t)a->P, nullptr, c.fov.levels).bytes
-		: carve_geom(a->variant, (size_t)a->P, nullptr, c.fov.levels).bytes);
+	char *gptr = a->geometry_resize(a->resize_user[0], keep == 2 ? carve_fov_full_geom((size_t)a->P, nullptr, c.fov.levels).bytes
+		: keep ? carve_fov_keep_geom((size_t)a->P, nullptr, c.fov.levels).bytes : carve_geom(a->variant, (size_t)a->P, nullptr, c.fov.levels).bytes);
 	char *iptr = a->image_resize(a->resize_user[2], keep ? carve_fov_keep_image(a->W, a->H, nullptr).bytes : carve_image(a->variant, a->W, a->H, nullptr).bytes);
 	if (!gptr || !iptr) { set_error("geometry/image resize callback returned null"); return FR_ERR_ALLOC; }
 	c.geom = carve_geom(a->variant, (size_t)a->P, gptr, c.fov.levels);
@@ -339,6 +340,7 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 		const FovKeepImage ki = carve_fov_keep_image(a->W, a->H, iptr);
 		c.keep_T = ki.final_T; c.keep_n = ki.n_contrib;
 		c.keep_acc = carve_fov_keep_geom((size_t)a->P, gptr, c.fov.levels).acc;
+		if (keep == 2) c.keep_mom = carve_fov_full_geom((size_t)a->P, gptr, c.fov.levels).mom; // (behind the keep layout: fr_geometry_bytes_fov_keep_full)
 		keep_state->geometry = gptr; keep_state->image = iptr;
 	}
 
@@ -405,12 +407,17 @@ extern "C" {
 
 int fr_forward_begin_fov(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **out)
 {
-	return forward_begin(a, ext, fov, nullptr, false, out);
+	return forward_begin(a, ext, fov, nullptr, 0, out);
 }
 
 int fr_forward_begin_fov_keep(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state, fr_frame **out)
 {
-	return forward_begin(a, ext, fov, state, true, out);
+	return forward_begin(a, ext, fov, state, 1, out);
+}
+
+int fr_forward_begin_fov_keep_full(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state, fr_frame **out)
+{
+	return forward_begin(a, ext, fov, state, 2, out);
 }
 
 int fr_forward_finish(fr_frame *f)
@@ -528,6 +535,20 @@ int fr_forward_fov_keep_call(fr_forward_args *a, const fr_forward_ext *ext, cons
 	const int rc = fr_forward_begin_fov_keep(a, ext, fov, state, &f);
 	if (rc) return rc;
 	return fr_forward_finish(f);
+}
+
+int fr_forward_fov_keep_full_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state)
+{
+	fr_frame *f = nullptr;
+	const int rc = fr_forward_begin_fov_keep_full(a, ext, fov, state, &f);
+	if (rc) return rc;
+	return fr_forward_finish(f);
+}
+
+size_t fr_geometry_bytes_fov_keep_full(int32_t P, int32_t levels)
+{
+	if (P < 0 || levels < 2 || levels > FR_FOV_LEVELS) { set_error("bad geometry_bytes_fov_keep_full arguments (levels 2 .. %d)", FR_FOV_LEVELS); return 0; }
+	return carve_fov_full_geom((size_t)P, nullptr, levels).bytes;
 }
 
 size_t fr_geometry_bytes_fov_keep(int32_t P, int32_t levels)
@@ -853,6 +874,35 @@ int fr_backward_fov_appearance(const fr_backward_fov_args *a)
 	if (!a->dL_dopacities) { set_error("backward_fov_appearance: dL_dopacities is null"); return FR_ERR_INVALID; }
 	if (!a->dL_dshs_dcs) { set_error("backward_fov_appearance: dL_dshs_dcs is null"); return FR_ERR_INVALID; }
 	return launch_backward_fov_appearance(a);
+}
+
+int fr_backward_fov(const fr_backward_fov_full_args *a)
+{
+	if (!a) { set_error("null arguments"); return FR_ERR_INVALID; }
+	if (a->size < sizeof(fr_backward_fov_full_args)) { set_error("fr_backward_fov_full_args.size is %u, expected at least %u", a->size, (unsigned)sizeof(fr_backward_fov_full_args)); return FR_ERR_INVALID; }
+	const fr_fov_state *st = a->state;
+	if (!st) { set_error("backward_fov: state is null"); return FR_ERR_INVALID; }
+	if (st->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", st->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
+	if ((st->variant & ~FR_FOV_STATE_FULL) != FR_VARIANT_FOV_PCHECK_OBB)
+	{ set_error("backward_fov: state.variant is %d, not %d (fov_pcheck_obb): not the state of a state-keeping foveated forward", st->variant & ~FR_FOV_STATE_FULL, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
+	if (!(st->variant & FR_FOV_STATE_FULL))
+	{ set_error("backward_fov: state.variant lacks FR_FOV_STATE_FULL: the state was not made by fr_forward_begin_fov_keep_full (its geometry workspace has no rows of moments)"); return FR_ERR_INVALID; }
+	if (st->levels < 2 || st->levels > FR_FOV_LEVELS)
+	{ set_error("backward_fov: state.levels is %d, not in 2..%d (levels 5 .. 8 would need a second row of sums)", st->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
+	if (st->P <= 0 || st->W <= 0 || st->H <= 0 || st->num_rendered < 0 || st->num_items < 0
+		|| st->num_items > 4 * ((st->W + FR_TILE - 1) / FR_TILE) * ((st->H + FR_TILE - 1) / FR_TILE))
+	{ set_error("backward_fov: state holds bad sizes (P=%d W=%d H=%d num_rendered=%d num_items=%d)", st->P, st->W, st->H, st->num_rendered, st->num_items); return FR_ERR_INVALID; }
+	if (!st->geometry || !st->image || (st->num_rendered > 0 && !st->binning)) { set_error("backward_fov: state.geometry / image / binning is null"); return FR_ERR_INVALID; }
+	if (a->P != st->P) { set_error("backward_fov: P is %d, the state's %d", a->P, st->P); return FR_ERR_INVALID; }
+	if (a->M < 1 || a->M > 16 || a->sh_degree < 0 || a->sh_degree > 3 || (a->sh_degree + 1) * (a->sh_degree + 1) > a->M)
+	{ set_error("backward_fov: M is %d and sh_degree %d (1 <= (sh_degree + 1)^2 <= M <= 16)", a->M, a->sh_degree); return FR_ERR_INVALID; }
+	const struct { const void *p; const char *name; } need[] = { { a->means3D, "means3D" }, { a->scales, "scales" }, { a->rotations, "rotations" },
+		{ a->M > 1 ? (const void *)a->shs_rest : (const void *)a, "shs_rest" }, { a->viewmatrix, "viewmatrix" }, { a->projmatrix, "projmatrix" }, { a->campos, "campos" },
+		{ a->background, "background" }, { a->dL_dpix, "dL_dpix" }, { a->dL_dopacities, "dL_dopacities" }, { a->dL_dshs_dcs, "dL_dshs_dcs" },
+		{ a->M > 1 ? (const void *)a->dL_dshs_rest : (const void *)a, "dL_dshs_rest" }, { a->dL_dmeans3D, "dL_dmeans3D" }, { a->dL_dscales, "dL_dscales" },
+		{ a->dL_drotations, "dL_drotations" }, { a->dL_dmeans2D, "dL_dmeans2D" } };
+	for (const auto &n : need) if (!n.p) { set_error("backward_fov: %s is null", n.name); return FR_ERR_INVALID; }
+	return launch_backward_fov_full(a);
 }
 
 int fr_backward_prefill(const fr_backward_args *a, void *fill_stream)

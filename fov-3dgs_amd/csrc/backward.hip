@@ -116,21 +116,26 @@ struct BwdFovArgs : BwdRenderArgs {
 	const float *tile_lv;           // [5][T] (ImageWS::tile_lv)
 	int T;
 	float start_blend, blend_width; // fr_foveation
+	float *mom = nullptr;           // the nine-sum pass (fr_backward_fov): [V][8] the items' rows of geometry moments (FovFullGeom::mom)
 };
 
 // One work item of the tile pass: k_render_bwd's and k_render_bwd_fov's kernels are this function.
 // LEAN (fr_backward_appearance): only the colour sums and M00 are formed and folded (fold8), into the same components of the row
 // (0, 1, 2 and 8); the five other moments and the products that serve only them are left out. Walk, staging, skip tests and the
 // recovery of T are the same code.
-// FOV (LEAN only; RF forward.cu:262-609 has no backward: the arithmetic is backward.cu:399-557's applied to k_render_fov's blend): the
+// FOV (RF forward.cu:262-609 has no backward: the arithmetic is backward.cu:399-557's applied to k_render_fov's blend): the
 // item carries ONE level state of its tile -- the entries take part with that level's row (opacity and colour: lvl[4 item + lev]), the
 // state's final_T / n_contrib come from its plane of the state-keeping forward, dL/dpixel is weighted with the state's share of the
 // pixel (w1 or 1 - w1 in a two-level tile: geometry and settings only, a constant of the derivative), the upper state skips the
 // Gaussians that do not exist at its level (forward.cu:399), and the four sums go to components 4 lev .. 4 lev + 3 of the row.
+// FOV and not LEAN (fr_backward_fov): all nine sums, folded as the plain pass folds them (fold18). The colour sums and M00 are the
+// level's and go where the lean pass puts them; the five moments are the GAUSSIAN's -- every level state that blends it adds to the
+// same five components of the item's second row (a.mom), and since the levels differ in their opacity the factor o_l is taken into
+// the moments here (dL/dG = o_l dL/dalpha_l: one product more per pair; M00 stays without it, it IS dL/do_l).
 template <bool CUTOFF, bool LEAN, bool FOV, typename Args>
 __device__ __forceinline__ void render_bwd_item(const Args &a)
 {
-	static_assert(!FOV || (LEAN && CUTOFF), "the foveated tile pass is the lean one");
+	static_assert(!FOV || CUTOFF, "the foveated blend has the power < -4.5 cutoff");
 	constexpr int PPL = 2;
 	constexpr int NV = LEAN ? 4 : 9; // sums per (band, entry) pair
 	__shared__ float4 s0[64];  // x, y, conic a, conic b
@@ -238,6 +243,12 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 	};
 	// the component of the row a sum goes to: (r, g, b, M00) of level `lev` are components 4 lev .. 4 lev + 3 of the foveated row
 	auto row_comp = [&](const int comp) { if constexpr (FOV) return 4 * lev + (comp == 8 ? 3 : comp); else return comp; };
+	// (the nine-sum foveated pass: where component `comp` of item `row` lives -- the level's quarter, or the item's row of moments)
+	auto sum_addr = [&](const int row, const int comp) -> float *
+	{
+		if constexpr (FOV && !LEAN) { if (comp >= 3 && comp < 8) return a.mom + 8 * (size_t)row + (comp - 3); }
+		return a.acc + 16 * (size_t)row + row_comp(comp);
+	};
 	// the forward blend's skip tests (k_render: outside the support, alpha < 1/255) as its ONE threshold on q = -power: the very same
 	// expression, so that the backward pass takes the gradient of exactly the pairs the forward pass blended
 	auto q_threshold = [&](float opacity, float &lq) { lq = logf(255.0f * opacity); return lq >= 0.0f ? (CUTOFF ? fminf(4.5f, lq) : lq) : 0.0f; };
@@ -259,7 +270,7 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 		{
 			const int comp = lane == 63 ? 8 : 2 * (lane >> 4) + sel;
 			const float val = lane == 63 ? t8 : (sel ? t1 : t0);
-			atomicAdd(a.acc + 16 * (size_t)row + comp, val); // nine lanes, one cache line
+			atomicAdd(sum_addr(row, comp), val); // nine lanes, one cache line (FOV: two)
 		}
 	};
 	for (int top = wave_last; top > 0; top -= 64)
@@ -349,8 +360,12 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 				if constexpr (LEAN) v[3] = m00;
 				else
 				{
-					const float m10 = m00 * dx, m20 = m10 * dx;
-					const bv2 wy = w * dy;
+					// (FOV: the moments carry the state's level's opacity, see above; m00 does not)
+					float mg = m00;
+					bv2 wg = w;
+					if constexpr (FOV) { wg = g1.y * w; mg = hsum(wg); }
+					const float m10 = mg * dx, m20 = m10 * dx;
+					const bv2 wy = wg * dy;
 					const float m01 = hsum(wy);
 					const float m11 = m01 * dx;
 					const float m02 = fmaf(wy.y, dy.y, wy.x * dy.x);
@@ -372,7 +387,7 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 					float val;
 					if constexpr (LEAN) val = fold8(pend, v, lane, e, comp, writer);
 					else val = fold18(pend, v, lane, e, comp, writer);
-					if (writer) atomicAdd(a.acc + 16 * (size_t)(e ? row : pend_row) + row_comp(comp), val); // eighteen (LEAN: eight) lanes, two cache lines
+					if (writer) atomicAdd(sum_addr(e ? row : pend_row, comp), val); // eighteen (LEAN: eight) lanes, two cache lines (FOV nine-sum: four)
 					have_pend = false;
 				}
 			}
@@ -395,6 +410,7 @@ __device__ __forceinline__ void render_bwd_item(const Args &a)
 template <bool CUTOFF, bool LEAN = false>
 __global__ void __launch_bounds__(64, 6) k_render_bwd(const BwdRenderArgs a) { render_bwd_item<CUTOFF, LEAN, false>(a); }
 __global__ void __launch_bounds__(64, 5) k_render_bwd_fov(const BwdFovArgs a) { render_bwd_item<true, true, true>(a); }
+__global__ void __launch_bounds__(64, 5) k_render_bwd_fov_full(const BwdFovArgs a) { render_bwd_item<true, false, true>(a); }
 
 // ---- per-Gaussian chain rule ------------------------------------------------------------------
 // Written from the matrix form of the forward pass rather than entry by entry.
@@ -511,7 +527,14 @@ __device__ __forceinline__ void sh_basis_grad(int deg, float x, float y, float z
 // sh_row: the Gaussian's 45 rest coefficients in LDS (k_preprocess_bwd fetched the wave's rows together), replaced in place by
 // their gradients (stored together as well); null: read / written here, per lane
 // sv: the lane's staging row of the narrow tensors (BwdPreArgs.small; null: every row stored on its own)
-__device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const int idx, const int slot, const float4 *stash, float *sh_row, float *sv)
+// FOVSUMS (k_fov_full_bwd, the foveated renderer's full backward pass): the item's sums do not come from a.acc but from `fs` -- the
+// colour sums already added over the item's levels with the clamped channels left out, the moments already times the levels'
+// opacities (k_render_bwd_fov_full) -- so the record's opacity and clamp bits, which a foveated frame does not have, are not read; the
+// opacity and DC gradients are per level and the caller's; colour is SH whenever there are rest coefficients (a.shs is not read).
+struct FovSums { float col[3]; float m10, m01, m20, m11, m02; };
+template <bool FOVSUMS = false>
+__device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const int idx, const int slot, const float4 *stash, float *sh_row, float *sv,
+	const FovSums *fs = nullptr)
 {
 	const size_t orow = a.row_sparse ? (size_t)slot : (size_t)idx; // the row of the gradient tensors this Gaussian's gradients go to
 	const float *vm = a.viewmatrix, *pm = a.projmatrix;
@@ -526,17 +549,26 @@ __device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const in
 		for (int i = 0; i < 6; i++) Sigma[i] = a.cov3D_precomp[6 * (size_t)idx + i];
 	}
 	// what k_render_bwd summed for this Gaussian
-	const float4 ac0 = a.acc[4 * (size_t)slot], ac1 = a.acc[4 * (size_t)slot + 1], ac2 = a.acc[4 * (size_t)slot + 2];
+	float4 ac0, ac1, ac2;
+	if constexpr (FOVSUMS)
+	{
+		ac0 = make_float4(fs->col[0], fs->col[1], fs->col[2], fs->m10); ac1 = make_float4(fs->m01, fs->m20, fs->m11, fs->m02);
+		ac2 = make_float4(0.f, 0.f, 0.f, 0.f);
+	}
+	else
+	{
+	ac0 = a.acc[4 * (size_t)slot]; ac1 = a.acc[4 * (size_t)slot + 1]; ac2 = a.acc[4 * (size_t)slot + 2];
 	// fr_backward is idempotent (the reference allocates fresh zeros per call, rasterize_points.cu:171-179): the row is read
 	// exactly once per call, so the reader leaves it cleared for a second backward pass over the same forward state
 	// (retain_graph, torch.autograd.grad twice). The last quarter (1 / |raw quaternion|) belongs to the forward pass and stays.
 	a.acc[4 * (size_t)slot] = a.acc[4 * (size_t)slot + 1] = a.acc[4 * (size_t)slot + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
+	}
 	const float g_col[3] = { ac0.x, ac0.y, ac0.z };
 	// k_render_bwd sums the moments M_ij = sum over pixels of G dL/dalpha dx^i dy^j (dx, dy: centre - pixel); with the conic Q and the
 	// opacity o of the forward pass (backward.cu:524-541): dL/dmean2D = -o Q (M10, M01) * (W / 2, H / 2), dL/dconic = -o/2 (M20, M11, M02)
 	// (the off-diagonal one counted once), dL/dopacity = M00
 	const float4 rq0 = a.rec[3 * (size_t)slot], rq1 = a.rec[3 * (size_t)slot + 1];
-	const float m10 = ac0.w, m01 = ac1.x, opac = rq1.y;
+	const float m10 = ac0.w, m01 = ac1.x, opac = FOVSUMS ? 1.0f : rq1.y; // (FOVSUMS: the opacity is in the moments already)
 	const float g_px = -opac * (rq0.z * m10 + rq0.w * m01) * (0.5f * a.W), g_py = -opac * (rq1.x * m01 + rq0.w * m10) * (0.5f * a.H);
 	const float gA = -0.5f * opac * ac1.y, gB = -0.5f * opac * ac1.z, gC = -0.5f * opac * ac1.w;
 	if (sv) { sv[0] = g_px; sv[1] = g_py; sv[2] = 0.0f; }
@@ -544,6 +576,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const in
 	if (a.row_sparse) a.dL_dmean2D[3 * orow + 2] = 0.0f; // (the dense tensors get their zeros from the fill)
 	// (raw parameters: through the sigmoid, o (1 - o), and below through exp and the normalisation -- what k_activate_bwd does
 	// for all P Gaussians, here only for the rows that are not zero anyway)
+	if constexpr (!FOVSUMS)
 	{
 		const float g_op = a.raw ? ac2.x * opac * (1.0f - opac) : ac2.x;
 		if (sv) sv[3] = g_op; else FR_ST(a.dL_dopacity + orow, g_op);
@@ -609,7 +642,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const in
 		g_mean.z += (pm[8] * iw - pm[11] * nx) * g_px + (pm[9] * iw - pm[11] * ny) * g_py;
 	}
 	// ---- colour from spherical harmonics (backward.cu:20-139)
-	if (a.colors_precomp == nullptr && a.shs != nullptr)
+	if (FOVSUMS ? a.shs_rest != nullptr : (a.colors_precomp == nullptr && a.shs != nullptr))
 	{
 		// Coefficients are read and their gradients written 16 bytes at a time in the concatenated order
 		// (k, channel) -> 3 k + channel: every lane works on its own Gaussian, i.e. its own cache lines, and 48 dword
@@ -622,7 +655,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const in
 		float *dsh0 = split ? a.dL_dsh + 3 * orow : a.dL_dsh + orow * a.M * 3;
 		const int nuse = 3 * ((a.D + 1) * (a.D + 1)) - 3; // rest floats the active degree reads / writes
 		// a channel clamped at zero in the forward pass passes no gradient (forward.cu:63-70)
-		const uint32_t clamp_bits = __float_as_uint(a.rec[3 * (size_t)slot + 2].z);
+		const uint32_t clamp_bits = FOVSUMS ? 0u : __float_as_uint(a.rec[3 * (size_t)slot + 2].z);
 		const float g[3] = { (clamp_bits & 1u) ? 0.f : g_col[0], (clamp_bits & 2u) ? 0.f : g_col[1], (clamp_bits & 4u) ? 0.f : g_col[2] };
 		const V3 off = { mean.x - a.campos[0], mean.y - a.campos[1], mean.z - a.campos[2] };
 		const float len2 = dot3(off, off), ilen = 1.0f / sqrtf(len2);
@@ -632,8 +665,9 @@ __device__ __forceinline__ void preprocess_bwd_one(const BwdPreArgs &a, const in
 #pragma unroll
 		for (int k = 0; k < 16; k++) { bas[k] = 0.f; grd[k] = { 0, 0, 0 }; }
 		sh_basis_grad(a.D, dir.x, dir.y, dir.z, bas, grd);
-		if (sv && split) { sv[14] = bas[0] * g[0]; sv[15] = bas[0] * g[1]; sv[16] = bas[0] * g[2]; }
-		else { FR_ST(dsh0, bas[0] * g[0]); FR_ST(dsh0 + 1, bas[0] * g[1]); FR_ST(dsh0 + 2, bas[0] * g[2]); }
+		if constexpr (FOVSUMS) (void)dsh0; // (the DC gradients are per level: the caller's)
+		else if (sv && split) { sv[14] = bas[0] * g[0]; sv[15] = bas[0] * g[1]; sv[16] = bas[0] * g[2]; }
+		else { FR_ST(dsh0,bas[0] * g[0]); FR_ST(dsh0 + 1, bas[0] * g[1]); FR_ST(dsh0 + 2, bas[0] * g[2]); }
 		V3 g_dir = { 0, 0, 0 };
 		if (sh_row != nullptr)
 		{
@@ -1324,17 +1358,21 @@ __global__ void __launch_bounds__(256) k_fov_appearance_bwd(const BwdFovAppArgs 
 	}
 }
 
-__global__ void __launch_bounds__(256) k_clear_item_rows(float4 *acc, const uint32_t *vis_count)
+// per: float4s a row (4: the rows of sums; 2: the rows of moments of the full backward pass)
+__global__ void __launch_bounds__(256) k_clear_item_rows(float4 *acc, const uint32_t *vis_count, const int per)
 {
-	const size_t n = 4 * (size_t)*vis_count;
+	const size_t n = (size_t)per * (size_t)*vis_count;
 	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 int launch_fov_keep_clear(FwdCtx &c)
 {
 	const size_t quads = 4 * (size_t)c.a->P;
 	const unsigned blocks = (unsigned)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048);
-	hipLaunchKernelGGL(k_clear_item_rows, dim3(blocks), dim3(256), 0, c.stream, c.keep_acc, c.geom.slab_ctr + 1);
-	return check_launch("clear_item_rows", c.stream, c.a->debug);
+	hipLaunchKernelGGL(k_clear_item_rows, dim3(blocks), dim3(256), 0, c.stream, c.keep_acc, c.geom.slab_ctr + 1, 4);
+	const int rc = check_launch("clear_item_rows", c.stream, c.a->debug);
+	if (rc || c.keep_mom == nullptr) return rc;
+	hipLaunchKernelGGL(k_clear_item_rows, dim3((blocks + 1) / 2), dim3(256), 0, c.stream, c.keep_mom, c.geom.slab_ctr + 1, 2);
+	return check_launch("clear_item_rows (moments)", c.stream, c.a->debug);
 }
 
 // One k_fill_zero over the dense outputs in front of the tile pass (as fr_backward_appearance: they are 28 L bytes a Gaussian), the
@@ -1401,6 +1439,163 @@ int launch_backward_fov_appearance(const fr_backward_fov_args *a)
 	const int pblocks = (int)((P + 255) / 256);
 	hipLaunchKernelGGL(k_fov_appearance_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
 	const int rc2 = check_launch("fov_appearance_bwd", stream, a->debug);
+	mark(2);
+	return rc2;
+}
+
+// ---- foveated full pass (fr_backward_fov) ----------------------------------------------------------------------------------------
+// Per visible-list item: the level quarters of its row of sums become dL/dopacities, dL/dshs_dcs and dL/dlevel_colours exactly as
+// k_fov_appearance_bwd forms them (same clamp rule: a stored level colour of 0 is a clamped channel); the colour sums of the levels
+// of the item's level range, clamped channels left out, are added up -- every level's colour is the SAME rest-SH part plus its own DC
+// term, so that sum is what the rest coefficients and the view direction receive (backward.cu:20-139); the five moments of the item's
+// second row give dL/dmean2D and dL/dconic (the opacities are in them already); and preprocess_bwd_one<true> runs k_preprocess_bwd's
+// chain rule on those. A foveated frame keeps no 64-byte row of (xyz | scale | rotation | 3D covariance) per item (GeomWS::cov3D is
+// the training variants'): the row is put together here from the model's tensors, the covariance recomputed as forward.cu:118-152
+// forms it. Both rows of sums are cleared again. Plain stores of the visible rows over ONE fill of all outputs (launch below).
+struct BwdFovFullArgs {
+	BwdPreArgs pre;            // camera, model tensors, the chain rule's outputs (what preprocess_bwd_one reads of it)
+	float4 *acc, *mom;
+	const float4 *lvl;
+	float *dL_dopacities, *dL_dshs_dcs, *dL_dlevel_colours;
+	int L;
+};
+
+__global__ void __launch_bounds__(256) k_fov_full_bwd(const BwdFovFullArgs a)
+{
+	const int V = (int)*a.pre.vis_count;
+	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x))
+	{
+		const uint32_t lr = a.pre.lrange[i];
+		if (lr == FR_ITEM_NONE) continue;
+		const int lo = (int)(lr & 0xffu), hi = (int)((lr >> 8) & 0xffu);
+		const int idx = (int)a.pre.vis_list[i];
+		const size_t g = (size_t)idx;
+		FovSums fs;
+		fs.col[0] = fs.col[1] = fs.col[2] = 0.0f;
+#pragma unroll
+		for (int l = 0; l < FR_FOV_LEVELS; l++)
+		{
+			if (l >= a.L) break;
+			const float4 s = a.acc[4 * (size_t)i + l];
+			a.acc[4 * (size_t)i + l] = make_float4(0.f, 0.f, 0.f, 0.f);
+			const bool used = l >= lo && l <= hi;
+			const float4 c = used ? a.lvl[4 * (size_t)i + l] : make_float4(0.f, 0.f, 0.f, 0.f);
+			const float o0 = c.x > 0.0f ? s.x : 0.0f, o1 = c.y > 0.0f ? s.y : 0.0f, o2 = c.z > 0.0f ? s.z : 0.0f;
+			fs.col[0] += o0; fs.col[1] += o1; fs.col[2] += o2;
+			const size_t o = g * (size_t)a.L + l;
+			FR_ST(a.dL_dopacities + o, s.w);
+			FR_ST(a.dL_dshs_dcs + 3 * o, FR_SH_C0 * o0); FR_ST(a.dL_dshs_dcs + 3 * o + 1, FR_SH_C0 * o1); FR_ST(a.dL_dshs_dcs + 3 * o + 2, FR_SH_C0 * o2);
+			if (a.dL_dlevel_colours != nullptr)
+			{
+				FR_ST(a.dL_dlevel_colours + 3 * o, s.x); FR_ST(a.dL_dlevel_colours + 3 * o + 1, s.y); FR_ST(a.dL_dlevel_colours + 3 * o + 2, s.z);
+			}
+		}
+		const float4 m0 = a.mom[2 * (size_t)i], m1 = a.mom[2 * (size_t)i + 1];
+		a.mom[2 * (size_t)i] = a.mom[2 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+		fs.m10 = m0.x; fs.m01 = m0.y; fs.m20 = m0.z; fs.m11 = m0.w; fs.m02 = m1.x;
+		// the item's row as k_bin leaves it for the training variants: (xyz, scale.x | scale.yz, rotation.rx | rotation.yz, Sigma xx xy |
+		// Sigma xz yy yz zz), Sigma = sum_i s_i^2 B_i B_i^T over the rows B_i of the matrix preprocess_bwd_one differentiates
+		const float *mp = a.pre.means3D + 3 * g, *sp = a.pre.scales + 3 * g;
+		const float4 q = ((const float4 *)a.pre.rotations)[g];
+		const float r = q.x, x = q.y, y = q.z, z = q.w;
+		const float sc[3] = { sp[0], sp[1], sp[2] };
+		const float B[3][3] = { { 1.f - 2.f * (y * y + z * z), 2.f * (x * y + r * z), 2.f * (x * z - r * y) },
+			{ 2.f * (x * y - r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z + r * x) },
+			{ 2.f * (x * z + r * y), 2.f * (y * z - r * x), 1.f - 2.f * (x * x + y * y) } };
+		float S[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+		{
+			const float sm = a.pre.scale_modifier * sc[k], s2 = sm * sm;
+			S[0] += s2 * B[k][0] * B[k][0]; S[1] += s2 * B[k][0] * B[k][1]; S[2] += s2 * B[k][0] * B[k][2];
+			S[3] += s2 * B[k][1] * B[k][1]; S[4] += s2 * B[k][1] * B[k][2]; S[5] += s2 * B[k][2] * B[k][2];
+		}
+		const float4 stash[4] = { make_float4(mp[0], mp[1], mp[2], sc[0]), make_float4(sc[1], sc[2], r, x), make_float4(y, z, S[0], S[1]),
+			make_float4(S[2], S[3], S[4], S[5]) };
+		preprocess_bwd_one<true>(a.pre, idx, i, stash, nullptr, nullptr, &fs);
+	}
+}
+
+int launch_backward_fov_full(const fr_backward_fov_full_args *a)
+{
+	const fr_fov_state *st = a->state;
+	hipStream_t stream = (hipStream_t)a->stream;
+	const int gx = (st->W + FR_TILE - 1) / FR_TILE, gy = (st->H + FR_TILE - 1) / FR_TILE, T = gx * gy;
+	const size_t P = (size_t)st->P;
+	const int L = st->levels;
+	GeomWS geom = carve_geom(FR_VARIANT_FOV_PCHECK_OBB, P, (char *)st->geometry, L);
+	ImageWS img = carve_image(FR_VARIANT_FOV_PCHECK_OBB, st->W, st->H, (char *)st->image);
+	BinWS bin = carve_bin(st->num_rendered, (char *)st->binning);
+	const FovFullGeom fg = carve_fov_full_geom(P, (char *)st->geometry, L);
+	const FovKeepImage ki = carve_fov_keep_image(st->W, st->H, (char *)st->image);
+	auto mark = [&](int i) { if (a->stage_events && a->stage_events[i]) (void)hipEventRecord((hipEvent_t)a->stage_events[i], stream); };
+	const size_t nrest = a->M > 1 ? 3 * (size_t)(a->M - 1) : 0;
+	{
+		// one fill over every output (the widest, the rest coefficients, is 180 bytes a Gaussian; the grid is sized by it)
+		struct { void *p; size_t words; } fills[] = { { a->dL_dopacities, P * L }, { a->dL_dshs_dcs, 3 * P * L }, { a->dL_dlevel_colours, 3 * P * L },
+			{ a->dL_dshs_rest, nrest * P }, { a->dL_dmeans3D, 3 * P }, { a->dL_dscales, 3 * P }, { a->dL_drotations, 4 * P }, { a->dL_dmeans2D, 3 * P },
+			{ a->dL_dconic, 4 * P } };
+		FillArgs fa; fa.n = 0;
+		size_t widest = 0;
+		for (auto &f : fills)
+			if (f.p && f.words)
+			{
+				if (((uintptr_t)f.p & 15) != 0)
+				{
+					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
+					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+					continue;
+				}
+				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
+				if (f.words > widest) widest = f.words;
+			}
+		static_assert(FR_FILL_MAX >= 9, "the full foveated pass clears nine tensors with one launch");
+		if (fa.n)
+		{
+			const size_t quads = (widest + 3) / 4;
+			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
+			hipLaunchKernelGGL(k_fill_zero, dim3(blocks ? blocks : 1), dim3(256), 0, stream, fa);
+			const int rcf = check_launch("fill_zero (fov full)", stream, a->debug);
+			if (rcf) return rcf;
+		}
+	}
+	mark(0);
+	if (st->num_rendered > 0 && st->num_items > 0)
+	{
+		BwdFovArgs r;
+		r.W = st->W; r.H = st->H; r.gx = gx; r.ranges = img.ranges; r.render_items = img.render_items; r.n_items = (uint32_t)st->num_items;
+		r.point_list = bin.point_list; r.rec = geom.rec;
+		r.bg = a->background; r.final_T = ki.final_T; r.n_contrib = ki.n_contrib; r.dL_dpix = a->dL_dpix;
+		r.acc = (float *)fg.acc; r.mom = (float *)fg.mom;
+		r.pairs = a->blend_pairs;
+		r.lvl = geom.lvl; r.tile_lv = img.tile_lv; r.T = T; r.start_blend = st->start_blend; r.blend_width = st->blend_width;
+		if (r.pairs != nullptr)
+		{
+			const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
+			if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+		}
+		hipLaunchKernelGGL(k_render_bwd_fov_full, dim3(r.n_items), dim3(64), 0, stream, r);
+		const int rc0 = check_launch("render_bwd_fov_full", stream, a->debug);
+		if (rc0) return rc0;
+	}
+	mark(1);
+	BwdFovFullArgs p = {}; // (every field of BwdPreArgs the chain rule does not get below: null / 0 -- no raw parameters, dense rows, no ranges)
+	p.pre.P = (int)P; p.pre.D = a->sh_degree; p.pre.M = a->M; p.pre.W = st->W; p.pre.H = st->H;
+	p.pre.tanfovx = a->tanfovx; p.pre.tanfovy = a->tanfovy;
+	p.pre.focal_y = st->H / (2.0f * a->tanfovy); p.pre.focal_x = st->W / (2.0f * a->tanfovx);
+	p.pre.scale_modifier = a->scale_modifier;
+	p.pre.means3D = a->means3D; p.pre.scales = a->scales; p.pre.rotations = a->rotations; p.pre.shs_rest = a->M > 1 ? a->shs_rest : nullptr;
+	p.pre.viewmatrix = a->viewmatrix; p.pre.projmatrix = a->projmatrix; p.pre.campos = a->campos;
+	p.pre.rec = geom.rec;
+	p.pre.dL_dmean2D = a->dL_dmeans2D; p.pre.dL_dconic = a->dL_dconic; p.pre.dL_dmean3D = a->dL_dmeans3D;
+	p.pre.dL_dsh_rest = a->dL_dshs_rest; p.pre.dL_dscale = a->dL_dscales; p.pre.dL_drot = a->dL_drotations;
+	p.pre.vis_list = geom.vis_list; p.pre.vis_count = geom.slab_ctr + 1; p.pre.lrange = geom.lrange;
+	p.pre.M0 = 1; p.pre.range_k = -1;
+	p.acc = fg.acc; p.mom = fg.mom; p.lvl = geom.lvl;
+	p.dL_dopacities = a->dL_dopacities; p.dL_dshs_dcs = a->dL_dshs_dcs; p.dL_dlevel_colours = a->dL_dlevel_colours; p.L = L;
+	const int pblocks = (int)((P + 255) / 256);
+	hipLaunchKernelGGL(k_fov_full_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
+	const int rc2 = check_launch("fov_full_bwd", stream, a->debug);
 	mark(2);
 	return rc2;
 }

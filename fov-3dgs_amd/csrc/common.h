@@ -209,6 +209,25 @@ __host__ __device__ inline FovKeepGeom carve_fov_keep_geom(size_t P, char *base,
 	g.bytes = off + 256;
 	return g;
 }
+// The full backward pass (fr_forward_begin_fov_keep_full / fr_backward_fov) keeps, BEHIND the keep layout above (none of its arrays
+// moves, fr_geometry_bytes_fov_keep answers what it answered), a second row of sums per item: the five geometry moments belong to
+// the Gaussian, not to a level, and have no place in a row whose four quarters are the four levels'.
+struct FovFullGeom {
+	float4 *acc;        // FovKeepGeom::acc
+	float4 *mom;        // [2P] one 32-byte row per item: (M10, M01, M20, M11 | M02, -, -, -), the moments of o_l G dL/dalpha_l about the splat
+	                    //      centre summed over every level state that blended the item (k_render_bwd_fov_full adds, k_fov_full_bwd reads
+	                    //      and clears; the forward call clears the rows of its items)
+	size_t bytes;
+};
+__host__ __device__ inline FovFullGeom carve_fov_full_geom(size_t P, char *base, int levels)
+{
+	const FovKeepGeom k = carve_fov_keep_geom(P, base, levels);
+	FovFullGeom g; size_t off = align_up(k.bytes);
+	g.acc = k.acc;
+	g.mom = (float4 *)(base + off); off = align_up(off + P * 2 * sizeof(float4));
+	g.bytes = off + 256;
+	return g;
+}
 struct FovKeepImage {
 	float *final_T;      // [2][W*H] per level state (plane 0: a single-level tile's state, state 1 of a two-level tile; plane 1: state 2):
 	uint32_t *n_contrib; // [2][W*H] the transmittance the state ended with, the 1-based list position of its last contributor
@@ -520,6 +539,7 @@ struct FwdCtx {
 	float *keep_T = nullptr;    // ... in these planes (FovKeepImage) ...
 	uint32_t *keep_n = nullptr;
 	float4 *keep_acc = nullptr; // ... and the items' rows of gradient sums (FovKeepGeom::acc) are cleared
+	float4 *keep_mom = nullptr; // fr_forward_begin_fov_keep_full: the items' rows of geometry moments (FovFullGeom::mom), cleared as well
 	GeomWS geom;
 	ImageWS img;
 	BinWS bin;
@@ -567,6 +587,8 @@ int launch_backward_appearance(const fr_backward_args *a);
 // fr_backward_fov_appearance: the foveated lean tile pass over the forward's work items and k_fov_appearance_bwd
 int launch_backward_fov_appearance(const fr_backward_fov_args *a);
 int launch_fov_keep_clear(FwdCtx &c); // the state-keeping forward: the rows of sums of the frame's items start as zeros
+// fr_backward_fov: the foveated nine-sum tile pass over the forward's work items and k_fov_full_bwd (the whole chain rule)
+int launch_backward_fov_full(const fr_backward_fov_full_args *a);
 // whole: clear every tensor in full (fr_backward_prefill: the caller's zeros come before a backward call that is told about them);
 // else the narrow tensors only where no 32-row group holds a visible Gaussian (the rest of them is k_preprocess_bwd's, backward.hip)
 int launch_gradient_fill(const fr_backward_args *a, hipStream_t fs, bool events, bool whole);

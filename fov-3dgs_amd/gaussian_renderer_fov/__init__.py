@@ -56,8 +56,13 @@ def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, hig
 
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, alpha=None, gazeArray=None,
            blending=None, starter=None, ender=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None,
-           foveation=None, appearance_only=False):
+           foveation=None, appearance_only=False, differentiable=False):
     """Render the scene for one gaze. Background tensor (bg_color) must be on the GPU.
+    differentiable (extension, opt-in): with autograd on, the image is differentiable in everything a fine-tune step of the composed
+    model moves -- pc.get_xyz, get_scaling, get_rotation, get_rest_features and the per-level `shs_dcs` [P,L,3] / `opacities` [P,L]
+    (fr_backward_fov; at most 4 layers) -- and "viewspace_points".grad is populated as the plain renderer populates it (what
+    densify.add_densification_stats reads). `highest_levels` must not require grad; refused together with appearance_only, with
+    packed=, and with more than 4 layers. The derivative is the appearance pass's (blend weights and level decisions are constants).
     appearance_only (extension, opt-in): with autograd on, the image is differentiable in the per-level appearance parameters --
     `opacities` [P,L] and `shs_dcs` [P,L,3] (fr_backward_fov_appearance; at most 4 layers) -- so the composed model can be fine-tuned
     through the renderer that ships it, e.g. against MetamericLoss at the frame's gaze. What the model `pc` hands over (positions,
@@ -74,6 +79,14 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
     bypass the version counter (`t.data.copy_()`, raw-pointer kernels, DLPack aliases): call invalidate_packed(pc) after
     such a write."""
     xyz = pc.get_xyz
+    if differentiable:
+        if appearance_only:
+            raise ValueError("differentiable and appearance_only exclude each other: appearance_only detaches what differentiable trains")
+        if packed is not None:
+            raise ValueError("differentiable: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
+        if foveation is not None and int(FoveationSettings(*foveation).levels) > 4:
+            raise ValueError("differentiable: the backward pass keeps one row of sums per Gaussian, i.e. at most 4 levels, "
+                             f"not {int(FoveationSettings(*foveation).levels)}")
     if appearance_only:
         if packed is not None:
             raise ValueError("appearance_only: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
@@ -134,7 +147,7 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
             means3D=means3D, means2D=means2D, shs_rest=shs_rest, colors_precomp=None, opacities=opacity, scales=scales,
             rotations=rotations, cov3D_precomp=None, shs_dcs=shs_dcs, highest_levels=highest_levels,
             gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed, foveation=foveation,
-            **({"appearance_only": True} if appearance_only else {}))
+            **({"appearance_only": True} if appearance_only else {}), **({"differentiable": True} if differentiable else {}))
     if ender is not None:
         ender.record()
 

@@ -382,11 +382,14 @@ def visibility_of(radii):
     return vis if vis is not None else radii > 0
 
 
-def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None):
+def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None, keep_full=False):
     """fr_forward_begin with the visibility mask as a second output where the library has it: the mask travels as an attribute of
     `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object).
     fov: the call's _native.Foveation (_foveation_struct), or None = today's entry points.
-    keep_state: a _native.FovState = the state-keeping foveated forward (fr_forward_begin_fov_keep), which fills it at finish."""
+    keep_state: a _native.FovState = the state-keeping foveated forward (fr_forward_begin_fov_keep), which fills it at finish;
+    keep_full: ... for the full backward pass (fr_forward_begin_fov_keep_full: a larger geometry workspace)."""
+    if keep_state is not None and keep_full and not _native.has_fov_full_backward(lib):
+        raise RuntimeError("fovraster: the loaded library has no full foveated backward pass (fr_backward_fov): rebuild it")
     if keep_state is not None and not _native.has_fov_backward(lib):
         raise RuntimeError("fovraster: the loaded library has no foveated backward pass (fr_backward_fov_appearance): rebuild it")
     if not _native.has_forward_ext(lib):
@@ -395,7 +398,8 @@ def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None):
     radii._fovraster_visibility = vis
     ext = _native.ForwardExt(C.sizeof(_native.ForwardExt), vis.data_ptr())  # (read during the call only)
     if keep_state is not None:
-        return lib.fr_forward_begin_fov_keep(C.byref(a), C.byref(ext), C.byref(fov) if fov is not None else None, C.byref(keep_state),
+        begin = lib.fr_forward_begin_fov_keep_full if keep_full else lib.fr_forward_begin_fov_keep
+        return begin(C.byref(a), C.byref(ext), C.byref(fov) if fov is not None else None, C.byref(keep_state),
                                              C.byref(handle))
     if fov is not None:
         return lib.fr_forward_begin_fov(C.byref(a), C.byref(ext), C.byref(fov), C.byref(handle))
@@ -444,7 +448,7 @@ class FrameInFlight:
 def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                    shs_dcs=None, highest_levels=None, gaze=(0.5, 0.5), alpha=0.05, persistent=False, loss_map=None,
                    sh_rest=None, packed=None, cur_level=0.0, raw_activations=False, list_consumed=None, no_stats=False, blend_pairs=None,
-                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False, keep_state=None):
+                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False, keep_state=None, keep_full=False):
     """First half of a forward call on the current stream -> FrameInFlight. count (variant original only): the counting render of
     LightGaussian's global-significance pruning -- the call also returns gaussians_count (exact hits per Gaussian) and the
     important_score (fovraster.h, fr_forward_args.gaussians_count); image and radii are those of the plain call.
@@ -459,7 +463,8 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
     (the caller's), and the fr_foveation struct made from them is kept beside the argument struct.
     foveation (foveated variant): a FoveationSettings, or None = the reference's constants through the entry points without settings.
     keep_state (foveated variant, training): a _native.FovState with its size set -- the state-keeping forward: the frame also keeps
-    what fr_backward_fov_appearance needs and fills the struct at finish() (the caller keeps it, and the workspaces, until backward)."""
+    what fr_backward_fov_appearance needs and fills the struct at finish() (the caller keeps it, and the workspaces, until backward);
+    keep_full: what fr_backward_fov needs (the full backward pass)."""
     lib = _native.load()
     _require_gpu(means3D)
     dev = means3D.device
@@ -579,7 +584,7 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if _stage_events_hook is not None:
             a.stage_events = _stage_events_hook()
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle, fov, keep_state)
+        rc = _begin_call(lib, a, P, dev, radii, handle, fov, keep_state, keep_full)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
         if keep_state is not None:
@@ -963,6 +968,52 @@ def _backward_fov_native(state, bg, grad_out_color, want_colours=False, stage_ev
     return g_op, g_dc, g_col
 
 
+def _backward_fov_full_native(state, rs, means3D, scales, rotations, shs_rest, grad_out_color, want_colours=False, want_conic=False,
+                              stage_events=None, blend_pairs=None, debug=False):
+    """fr_backward_fov over the state of a _full state-keeping forward (whose workspaces the caller still holds), with the model and the
+    settings `rs` that forward rendered -> dict of dL_dopacities [P,L], dL_dshs_dcs [P,L,3], dL_dlevel_colours [P,L,3] or None,
+    dL_dshs_rest [P,M-1,3], dL_dmeans3D [P,3], dL_dscales [P,3], dL_drotations [P,4], dL_dmeans2D [P,3], dL_dconic [P,4] or None, on the
+    current stream. Every tensor is written in full by the library (zero rows included)."""
+    lib = _native.load()
+    if not _native.has_fov_full_backward(lib):
+        raise RuntimeError("fovraster: the loaded library has no full foveated backward pass (fr_backward_fov): rebuild it")
+    dev = grad_out_color.device
+    P, L = int(state.P), int(state.levels)
+    z = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)) if P != 0 else \
+        (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
+    if POISON_GRADIENTS and P != 0:
+        z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        m, sc, ro, rest = (_f32(t.detach(), dev) for t in (means3D, scales, rotations, shs_rest))
+        nrest = 0 if rest is None else int(rest.size(1))
+        out = dict(dL_dopacities=z(P, L), dL_dshs_dcs=z(P, L, 3), dL_dlevel_colours=z(P, L, 3) if want_colours else None,
+                   dL_dshs_rest=z(P, nrest, 3), dL_dmeans3D=z(P, 3), dL_dscales=z(P, 3), dL_drotations=z(P, 4), dL_dmeans2D=z(P, 3),
+                   dL_dconic=z(P, 4) if want_conic else None)
+        if P != 0:
+            a = _native.BackwardFovFullArgs()
+            a.size, a.debug = C.sizeof(_native.BackwardFovFullArgs), int(bool(debug))
+            a.state = C.pointer(state)
+            a.P, a.M, a.sh_degree = P, 1 + nrest, int(rs.sh_degree)
+            a.tanfovx, a.tanfovy, a.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
+            sh_ = torch.cuda.current_stream(dev).cuda_stream
+            small = [_f32_small(t, dev, sh_) for t in (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg)]
+            dpix = _f32(grad_out_color, dev)
+            a.means3D, a.scales, a.rotations, a.shs_rest = _ptr(m), _ptr(sc), _ptr(ro), _ptr(rest)
+            a.viewmatrix, a.projmatrix, a.campos, a.background = (_ptr(t) for t in small)
+            a.dL_dpix = dpix.data_ptr()
+            for k, t in out.items():
+                setattr(a, k, _ptr(t) if t is not None and t.numel() else None)
+            a.stream = sh_
+            if stage_events is not None:
+                a.stage_events = stage_events
+            if blend_pairs is not None:
+                a.blend_pairs = blend_pairs.data_ptr()
+            rc = lib.fr_backward_fov(C.byref(a))
+            if rc != 0:
+                raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
+    return out
+
+
 def visible_rows(variant, P, geomBuffer, num_candidates):
     """The Gaussian indices (int64 [num_candidates], increasing) of the rows of a row-sparse backward call."""
     lib = _native.load()
@@ -1226,13 +1277,15 @@ def _make_fov():
         @staticmethod
         def forward(ctx, means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                     raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending, packed=None, foveation=None,
-                    appearance_only=False, grad_mode=True):
+                    appearance_only=False, grad_mode=True, differentiable=False):
             args = (variant_id, raster_settings, means3D, shs_rest, colors_precomp, opacities, scales, rotations,
                     cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha))
             # appearance_only (extension): the state-keeping forward over a leased workspace set, as the plain variants' training
             # calls; backward is fr_backward_fov_appearance (grad_mode = torch.is_grad_enabled() at the call site)
             ctx.keep = bool(appearance_only) and grad_mode and (ctx.needs_input_grad[4] or ctx.needs_input_grad[9])
-            if ctx.keep:
+            # differentiable (extension): the same over the larger geometry workspace; backward is fr_backward_fov, the whole chain rule
+            ctx.full = bool(differentiable) and grad_mode and any(ctx.needs_input_grad[i] for i in (0, 1, 2, 4, 5, 6, 9))
+            if ctx.keep or ctx.full:
                 ctx.set_materialize_grads(False)
                 state = _native.FovState()
                 state.size = C.sizeof(_native.FovState)
@@ -1240,14 +1293,18 @@ def _make_fov():
                 if ev is not None:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
-                res = _forward_begin(*args, persistent=False, foveation=foveation, keep_state=state).finish()
+                res = _forward_begin(*args, persistent=False, foveation=foveation, keep_state=state, keep_full=ctx.full).finish()
                 if ev is not None:
                     e1.record()
                     ev.append(("fwd", e0, e1))
                 color, radii = res[1], res[2]
                 ctx.fov_state, ctx.ws_lease, ctx.raster_settings = state, res[-1], raster_settings
                 ctx.shapes = (tuple(opacities.shape), tuple(shs_dcs.shape))
-                ctx.save_for_backward(res[3], res[4], res[5])  # the workspaces the state points into
+                if ctx.full:  # (the chain rule reads the model again: the frame keeps no copy of it)
+                    ctx.shapes = ctx.shapes + tuple(tuple(t.shape) for t in (means3D, shs_rest, scales, rotations))
+                    ctx.save_for_backward(res[3], res[4], res[5], means3D, scales, rotations, shs_rest)
+                else:
+                    ctx.save_for_backward(res[3], res[4], res[5])  # the workspaces the state points into
                 ctx.mark_non_differentiable(radii)
                 return color, radii
             if raster_settings.debug:
@@ -1269,20 +1326,31 @@ def _make_fov():
         def backward(ctx, grad_out_color, _):
             # RF/diff_gaussian_rasterization_fov_pcheck_obb/__init__.py:128-187: the foveated extension is
             # inference-only and hands back None for every input
-            if not ctx.keep or grad_out_color is None:
-                return (None,) * 18
+            if not (ctx.keep or ctx.full) or grad_out_color is None:
+                return (None,) * 19
             ev = _call_events
             if ev is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
             _ws = ctx.saved_tensors  # (alive until here: the state holds their addresses)
-            g_op, g_dc, _ = _backward_fov_native(ctx.fov_state, ctx.raster_settings.bg, grad_out_color,
-                                                 stage_events=_bwd_events_hook() if _bwd_events_hook is not None else None,
-                                                 debug=ctx.raster_settings.debug)
+            if ctx.full:
+                g = _backward_fov_full_native(ctx.fov_state, ctx.raster_settings, *_ws[3:7], grad_out_color,
+                                              stage_events=_bwd_events_hook() if _bwd_events_hook is not None else None,
+                                              debug=ctx.raster_settings.debug)
+                g_op, g_dc = g["dL_dopacities"], g["dL_dshs_dcs"]
+            else:
+                g_op, g_dc, _ = _backward_fov_native(ctx.fov_state, ctx.raster_settings.bg, grad_out_color,
+                                                     stage_events=_bwd_events_hook() if _bwd_events_hook is not None else None,
+                                                     debug=ctx.raster_settings.debug)
             if ev is not None:
                 e1.record()
                 ev.append(("bwd", e0, e1))
-            grads = [None] * 18
+            grads = [None] * 19
+            if ctx.full:
+                for i, k, shape in ((0, "dL_dmeans3D", ctx.shapes[2]), (1, "dL_dmeans2D", ctx.shapes[2]), (2, "dL_dshs_rest", ctx.shapes[3]),
+                                    (5, "dL_dscales", ctx.shapes[4]), (6, "dL_drotations", ctx.shapes[5])):
+                    if ctx.needs_input_grad[i]:
+                        grads[i] = g[k].reshape(shape)
             if ctx.needs_input_grad[4]:
                 grads[4] = g_op.reshape(ctx.shapes[0])
             if ctx.needs_input_grad[9]:
@@ -1291,7 +1359,7 @@ def _make_fov():
 
     def rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending,
-                            packed=None, foveation=None, appearance_only=False):
+                            packed=None, foveation=None, appearance_only=False, differentiable=False):
         if not torch.is_grad_enabled() and not raster_settings.debug:
             # (inference: no graph to build -- the autograd machinery around an inference-only extension is 15 us of host time a
             # frame on a path where the host sets the pace, see OVERLAP_SUCCESSIVE_FRAMES)
@@ -1301,7 +1369,7 @@ def _make_fov():
             return res[1], res[2]
         return _RasterizeGaussians.apply(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                         blending, packed, foveation, appearance_only, torch.is_grad_enabled())
+                                         blending, packed, foveation, appearance_only, torch.is_grad_enabled(), differentiable)
 
     class GaussianRasterizer(nn.Module):
         def __init__(self, raster_settings):
@@ -1314,13 +1382,27 @@ def _make_fov():
 
         def forward(self, means3D, means2D, opacities, shs_rest=None, colors_precomp=None, scales=None,
                     rotations=None, cov3D_precomp=None, shs_dcs=None, highest_levels=None, gazeArray=None,
-                    alpha=None, blending=None, packed=None, foveation=None, appearance_only=False):
+                    alpha=None, blending=None, packed=None, foveation=None, appearance_only=False, differentiable=False):
             """foveation (extension): a FoveationSettings -- layer count and display geometry --, or None = the reference's
             constants (4 layers, maximum pooling size 12, a display 2 wide seen from 1, blend band 0.5 / 0.5).
             appearance_only (extension, opt-in): with autograd on, the image is differentiable in opacities [P,L] and shs_dcs [P,L,3]
             (fr_backward_fov_appearance; at most 4 layers); every other input gets None, and one that requires grad is refused. Without
-            the flag the call is the reference's inference-only one."""
+            the flag the call is the reference's inference-only one.
+            differentiable (extension, opt-in): with autograd on, the image is differentiable in means3D, means2D (the viewspace
+            points), scales, rotations, shs_rest, opacities [P,L] and shs_dcs [P,L,3] (fr_backward_fov; at most 4 layers); needs
+            scales / rotations and shs_rest (no precomputed covariance or colours); highest_levels must not require grad."""
             raster_settings = self.raster_settings
+            if differentiable:
+                if appearance_only:
+                    raise ValueError("differentiable and appearance_only exclude each other: appearance_only detaches what differentiable trains")
+                if packed is not None:
+                    raise ValueError("differentiable: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
+                if foveation is not None and int(foveation.levels) > 4:
+                    raise ValueError(f"differentiable: the backward pass keeps one row of sums per Gaussian, i.e. at most 4 levels, not {int(foveation.levels)}")
+                if colors_precomp is not None or cov3D_precomp is not None:
+                    raise ValueError("differentiable: the chain rule runs from scales / rotations and the SH coefficients (no colors_precomp / cov3D_precomp)")
+                if highest_levels is not None and highest_levels.requires_grad:
+                    raise ValueError("differentiable: highest_levels requires grad, but the level filter is a decision, not a value: detach it")
             if appearance_only:
                 if packed is not None:
                     raise ValueError("appearance_only: a packed model is inference-only -- training renders from the ordinary tensors (packed=None)")
@@ -1339,7 +1421,7 @@ def _make_fov():
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                       blending, packed, foveation, appearance_only))
+                                       blending, packed, foveation, appearance_only, differentiable))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 

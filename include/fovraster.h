@@ -455,6 +455,64 @@ typedef struct fr_backward_fov_args {
 } fr_backward_fov_args;
 int fr_backward_fov_appearance(const fr_backward_fov_args *args);
 
+/* The FULL backward pass of the foveated renderer (extension): beside the per-level appearance parameters, the shared geometry
+ * (means3D, scales, rotations) and the rest SH coefficients of a composed model get their gradients through the renderer that ships
+ * it. The derivative is the one fr_backward_fov_appearance takes (above: w1 a constant, state 1 starting finished where est > l2,
+ * the upper state's existence skip, the power < -4.5 cutoff, the undifferentiated min(0.99, o G), T recovered by division, the
+ * background term); per blended (pixel, level state, Gaussian) pair it forms the nine values of backward.cu:503-554. The three
+ * colour sums and M00 are the state's LEVEL's (the level's quarter of the item's row, as above); the five moments M10 M01 M20 M11
+ * M02 are the GAUSSIAN's: they are summed over every level state that blends it, with dL/dG = o_l dL/dalpha_l, into a second row.
+ *
+ * fr_forward_begin_fov_keep_full / fr_forward_fov_keep_full_call: the state-keeping forward with a LARGER geometry workspace,
+ * fr_geometry_bytes_fov_keep_full: the keep layout with, behind it, one 32-byte row of moments per Gaussian (the image workspace is
+ * fr_image_bytes_fov_keep's). Image and radii are those of the plain call bit for bit (the same kernels as the keep call). Nothing
+ * else is kept: the chain rule RECOMPUTES the 3D covariance from the scales and rotations it is handed (the inference frame's
+ * geometry rows have no room for it), so fr_backward_fov must be given the model the forward call rendered. The state's variant reads
+ * FR_VARIANT_FOV_PCHECK_OBB | FR_FOV_STATE_FULL; fr_backward_fov_appearance REFUSES such a state (its variant test), and
+ * fr_backward_fov refuses a plain keep state: each pass clears only the rows it owns. Refusals as fr_forward_begin_fov_keep's. */
+#define FR_FOV_STATE_FULL 0x100
+int fr_forward_begin_fov_keep_full(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state, fr_frame **frame);
+int fr_forward_fov_keep_full_call(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *state);
+size_t fr_geometry_bytes_fov_keep_full(int32_t P, int32_t levels);
+/* fr_backward_fov: size = sizeof(fr_backward_fov_full_args).
+ *   state                 the _full forward call's, unchanged
+ *   P, M, sh_degree       Gaussians (= state->P), SH coefficients per Gaussian INCLUDING the DC one (16: shs_rest is [P,M-1,3]), active degree
+ *   means3D [P,3], scales [P,3], rotations [P,4]   required: the activated inputs of the forward call
+ *   shs_rest [P,M-1,3]    required when M > 1
+ *   viewmatrix, projmatrix [16], campos [3], background [3], dL_dpix [3,H,W]   required; tanfovx / tanfovy / scale_modifier as forward
+ *   dL_dopacities [P,L], dL_dshs_dcs [P,L,3]       required, as fr_backward_fov_appearance's; dL_dlevel_colours [P,L,3] or NULL
+ *   dL_dshs_rest [P,M-1,3] required when M > 1: the SH backward (backward.cu:20-139) applied to the sum over the item's level range
+ *                         of [colour_l > 0] dL/dcolour_l; coefficients above sh_degree are exact zeros
+ *   dL_dmeans3D [P,3]     required: view-direction term of the SH backward (fed with the same masked sum) + projection term
+ *                         (backward.cu:346-396) + covariance term (backward.cu:144-274: clamped tangents and the 1e-7 guard as there)
+ *   dL_dscales [P,3], dL_drotations [P,4]          required: w.r.t. the activated inputs, scale_modifier honoured (backward.cu:278-341;
+ *                         dL_dscales is the reference's dL/d(scale_modifier scale), as fr_backward's: backward.cu:295-325)
+ *   dL_dmeans2D [P,3]     required: as fr_backward returns it (x, y in NDC units, third component 0); dL_dconic [P,4] or NULL
+ *   stage_events          optional [3]: in front of the tile pass, between the passes, behind them; blend_pairs optional [T]
+ * Every output is dense and written in full, zero rows included: ONE fill over all of them in front of the tile pass, then plain
+ * stores of the visible rows (the whole-line scheme of fr_backward is tied to k_preprocess_bwd's staging; chosen for simplicity, as
+ * fr_backward_appearance). The per-Gaussian pass clears the sums it read: a second call over one state repeats the first. Never
+ * synchronises. FR_ERR_INVALID before anything is enqueued, naming the field: state NULL / of another variant / not made by the
+ * _full forward / with levels > 4; P != state->P; a required pointer NULL. (A packed model cannot get here: the _full forward
+ * refuses packed_geom / packed_colour / packed_cull.) */
+typedef struct fr_backward_fov_full_args {
+	uint32_t size;
+	int32_t debug;
+	const fr_fov_state *state;
+	int32_t P, M, sh_degree;
+	float tanfovx, tanfovy, scale_modifier;
+	const float *means3D, *scales, *rotations, *shs_rest;
+	const float *viewmatrix, *projmatrix, *campos;
+	const float *background;
+	const float *dL_dpix;
+	float *dL_dopacities, *dL_dshs_dcs, *dL_dlevel_colours;
+	float *dL_dshs_rest, *dL_dmeans3D, *dL_dscales, *dL_drotations, *dL_dmeans2D, *dL_dconic;
+	void *stream;
+	void **stage_events;
+	uint32_t *blend_pairs;
+} fr_backward_fov_full_args;
+int fr_backward_fov(const fr_backward_fov_full_args *args);
+
 int fr_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, const float *projmatrix,
 	uint8_t *present /* [P] bool */, void *stream);
 
