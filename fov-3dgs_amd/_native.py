@@ -184,7 +184,7 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_forward_begin_fov", "fr_forward_fov_call", "fr_geometry_bytes_fov", "fr_geometry_level_colours_hi", "fr_pack_colour_fov",
            "fr_hvs_workspace_floats", "fr_hvs_forward", "fr_hvs_backward",
            "fr_hvs_forward_resized", "fr_hvs_backward_resized", "fr_hvs_resized_backward_floats",
-           "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward",
+           "fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward", "fr_hvs_fov_backward_plan",
            "fr_quality_blocks", "fr_quality_forward", "fr_quality_finish",
            "fr_scale_decay_blocks", "fr_scale_decay_forward", "fr_scale_decay_backward", "fr_opacity_cap",
            "fr_select_kth", "fr_mask_le", "fr_volume", "fr_v_importance",
@@ -280,6 +280,8 @@ def load():
     lib.fr_hvs_fov_forward.restype = C.c_int
     lib.fr_hvs_fov_backward.argtypes = _fov + [_FP] * 7 + [C.c_void_p]
     lib.fr_hvs_fov_backward.restype = C.c_int
+    lib.fr_hvs_fov_backward_plan.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int64)]
+    lib.fr_hvs_fov_backward_plan.restype = C.c_int
     for n in ("fr_geometry_bytes",):
         getattr(lib, n).argtypes = [C.c_int32, C.c_int32]
         getattr(lib, n).restype = C.c_size_t

@@ -62,6 +62,7 @@ struct FovLevel
 	long long part; int part_n;
 	long long glow, g[FOV_MAXK + 1], gpart[FOV_MAXK + 1]; // backward workspace: [2,nmc,cells_k] and [S_k,2,nmc,cells_k]
 	int G[FOV_MAXK + 1], S[FOV_MAXK + 1], R[FOV_MAXK + 1];
+	int rows[FOV_MAXK + 1], cols[FOV_MAXK + 1];   // the footprint bound G, S and R were sized for (fr_hvs_fov_backward_plan reports it)
 };
 
 struct FovPlan
@@ -112,6 +113,7 @@ static int fov_plan(int H, int W, int L, int nb, FovPlan *p)
 			c.q[k] = ws; ws += cells;
 			// the footprint of a texel: the pixels whose two bilinear taps can name it (k_fov_bwd_up), all of them for the 1x1 level
 			const int rows = k == K ? h : min(h, (int)(2.0 * h / c.h[k]) + 6), cols = k == K ? w : min(w, (int)(2.0 * w / c.w[k]) + 6);
+			v.rows[k] = rows; v.cols[k] = cols;
 			v.G[k] = fov_group((long long)rows * cols);
 			int S = (int)min((long long)rows, ((long long)rows * cols + (long long)v.G[k] * 512 - 1) / ((long long)v.G[k] * 512));
 			v.R[k] = (rows + S - 1) / S;
@@ -461,6 +463,19 @@ extern "C" int64_t fr_hvs_fov_workspace_floats(int32_t Hs, int32_t Ws, int32_t H
 	if (which == 3) return 2 * p.lod_doubles;
 	set_error("hvs_fov: which must be 0 (forward state), 1 (backward workspace), 2 (partial sums) or 3 (LOD maps)");
 	return -1;
+}
+
+extern "C" int fr_hvs_fov_backward_plan(int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t level, int32_t k, int64_t *out)
+{
+	FovPlan p;
+	if (fov_plan(H, W, n_levels, n_orientations, &p) != FR_OK) return FR_ERR_INVALID;
+	if (level < 0 || level > p.L - 2) { set_error("hvs_fov_backward_plan: pyramid level %d outside 0..%d", level, p.L - 2); return FR_ERR_INVALID; }
+	const FovLevel &v = p.lv[level];
+	if (k < 1 || k > v.a.c.K) { set_error("hvs_fov_backward_plan: chain level %d outside 1..%d (pyramid level %d)", k, v.a.c.K, level); return FR_ERR_INVALID; }
+	if (!out) { set_error("hvs_fov_backward_plan: out is null"); return FR_ERR_INVALID; }
+	out[0] = v.a.c.K; out[1] = v.a.c.h[k]; out[2] = v.a.c.w[k]; out[3] = v.rows[k]; out[4] = v.cols[k];
+	out[5] = v.G[k]; out[6] = v.S[k]; out[7] = v.R[k]; out[8] = v.g[k]; out[9] = v.gpart[k];
+	return FR_OK;
 }
 
 extern "C" int fr_hvs_fov_forward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double alpha, double real_image_width, double real_viewing_distance,

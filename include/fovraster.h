@@ -609,8 +609,18 @@ int64_t fr_hvs_resized_backward_floats(int32_t Hs, int32_t Ws, int32_t H, int32_
  *   call fills it (kernels on `stream`; a gaze change costs no host synchronisation).
  * backward: as fr_hvs_backward / fr_hvs_backward_resized, from the two states and the LOD maps of the forward. Every sum is a
  *   gather in a fixed order, with no atomics and no zero fill: the same bits on every run.
- * The number of launches depends on H, W and n_levels only. */
+ * The number of launches depends on H, W and n_levels only.
+ * fr_hvs_fov_backward_plan(.., level, k, out): host only, no GPU call. What the backward pass does at chain level k (1 .. K) of
+ *   pyramid level `level` (0 .. n_levels - 2) of an H x W call, as ten numbers: out[0] = K, the chain's last level; out[1], out[2] =
+ *   h_k, w_k; out[3], out[4] = rows, cols, the bound of a texel's footprint in pixels that the next three were sized for;
+ *   out[5] = G, the lanes that share a texel (1, 8 or 64); out[6] = S, the row slices a footprint is cut into, and out[7] = R, the
+ *   rows of a slice (the last slice runs to the footprint's end); out[8] = the offset in floats of g[k], [2,nmc,h_k,w_k] (the
+ *   gradient of the mean chain, then of the chain of the square; nmc = 3 n_orientations, + 3 at level 0), in the backward
+ *   workspace, out[9] = that of the slices' partial sums, [S,2,nmc,h_k,w_k]. Both are valid after fr_hvs_fov_backward (the
+ *   offsets do not depend on Hs, Ws). FR_ERR_INVALID for a size fr_hvs_fov_workspace_floats refuses, a level or k out of range
+ *   or a null out. For tests and tools. */
 int64_t fr_hvs_fov_workspace_floats(int32_t Hs, int32_t Ws, int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t which);
+int fr_hvs_fov_backward_plan(int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t level, int32_t k, int64_t *out);
 int fr_hvs_fov_forward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double alpha, double real_image_width, double real_viewing_distance,
 	int32_t mode, double gaze_x, double gaze_y, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb, const float *filters,
 	const float *img, const float *target, float *state_img, float *state_target, float *lod, int32_t lod_valid, float *partials, float *out,

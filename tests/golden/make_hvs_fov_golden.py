@@ -23,6 +23,7 @@ sys.path.insert(0, "/root/reference/metamer")
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from odak_perception import MetamericLoss  # noqa: E402
 from tests import hvs_fov_ref, hvs_ref  # noqa: E402
+from tests.hvs_fov_cases import pictures  # noqa: E402  (the noise width is a parameter)
 
 # (H, W, levels, orientations, alpha, mode, type, gaze, width, distance, colour space)
 CASES = [(32, 64, 5, 6, 0.05, "quadratic", "MSE", (0.5, 0.5), 1.0, 0.5, "RGB"),      # F0: HVSLoss's defaults; deeper levels all-identity
@@ -38,16 +39,6 @@ KINK_SHARE = 2e-7  # make_hvs_golden.py's
 REF_L2 = 2e-5
 AMPLITUDES = (0.5, 1.0, 2.0, 4.0)   # (the picture is clipped to [0, 1]: the larger ones approach two-valued noise)
 SEEDS = 40
-
-
-def pictures(H, W, seed, amp):
-    """make_hvs_golden.pictures with the noise width as a parameter"""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.meshgrid(np.linspace(0, 3, H), np.linspace(0, 2, W), indexing="ij")
-    base = np.stack([0.5 + 0.2 * np.sin(xx * (c + 1) + yy) * np.cos(yy * 1.7 - c) for c in range(3)])
-    tgt = np.clip(base + amp * (rng.random(base.shape) - 0.5), 0, 1)
-    img = np.clip(tgt + 0.05 * rng.standard_normal(base.shape), 0, 1)
-    return np.round(img * 65535).astype(np.uint16)[None], np.round(tgt * 65535).astype(np.uint16)[None]
 
 
 def reference(case):

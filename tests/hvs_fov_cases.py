@@ -55,5 +55,17 @@ def yardstick(i):
     return out
 
 
+def pictures(H, W, seed, amp):
+    """the fixtures' picture pair as 16-bit arrays [1,3,H,W] (image, target): smooth colour plus uniform noise of width `amp`,
+    clipped to [0, 1] (tests/golden/make_hvs_golden.pictures with the noise width as a parameter); the generators draw their
+    pictures here, and a fixture that stores only (seed, amp) gets the same ones back"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.linspace(0, 3, H), np.linspace(0, 2, W), indexing="ij")
+    base = np.stack([0.5 + 0.2 * np.sin(xx * (c + 1) + yy) * np.cos(yy * 1.7 - c) for c in range(3)])
+    tgt = np.clip(base + amp * (rng.random(base.shape) - 0.5), 0, 1)
+    img = np.clip(tgt + 0.05 * rng.standard_normal(base.shape), 0, 1)
+    return np.round(img * 65535).astype(np.uint16)[None], np.round(tgt * 65535).astype(np.uint16)[None]
+
+
 def max_abs(got, want):
     return float(np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)).max())

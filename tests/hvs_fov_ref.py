@@ -82,13 +82,26 @@ def mip_chain(x):
     return chain
 
 
-def blur(x, lod):
+def blur(x, lod, chain_out=None, cut=None):
     """radially_varying_blur.py:111-140: out = up_K where lod >= K, else (1 - f) up_l + f up_{l+1}, l = floor(lod),
-    f = fmod(lod, 1); up_k is level k bilinearly up-sampled straight to full size, up_K the constant"""
+    f = fmod(lod, 1); up_k is level k bilinearly up-sampled straight to full size, up_K the constant.
+    chain_out: a list that receives the mip chain [m_0 .. m_K] (the tensors of the graph: after backward() m_k.grad is the loss's
+    gradient with respect to chain level k, what csrc/hvs_fov.hip keeps as g[k]).
+    cut = (k, y0, y1): rows y0 .. y1 - 1 of up_k are detached, so those pixels pass nothing back to level k THROUGH up_k (the
+    forward value is unchanged): the defect of a backward pass that skips those rows of level k's footprints."""
     chain = mip_chain(x)
+    if chain_out is not None:
+        for m in chain[1:]:
+            if m.requires_grad:
+                m.retain_grad()
+        chain_out.append(chain)
     K = len(chain) - 1
     size = x.shape[-2:]
     up = [x] + [F.interpolate(m, size=size, mode="bilinear", align_corners=False) for m in chain[1:K]] + [chain[K].expand_as(x)]
+    if cut is not None:
+        k, y0, y1 = cut
+        u = up[k]
+        up[k] = torch.cat([u[..., :y0, :], u[..., y0:y1, :].detach(), u[..., y1:, :]], dim=-2)
     frac = torch.fmod(lod, 1.0)
     out = torch.zeros_like(x)
     for l in range(K + 1):
@@ -101,10 +114,11 @@ def blur(x, lod):
     return out
 
 
-def find_stats(x, lod):
-    """metameric_loss.py:101-109 -> (mean, std, var before the clamp)"""
-    mean = blur(x, lod)
-    var = blur(x * x, lod) - mean * mean
+def find_stats(x, lod, tap=None):
+    """metameric_loss.py:101-109 -> (mean, std, var before the clamp). tap: see stats_maps"""
+    cut = None if tap is None else tap.get("cut")
+    mean = blur(x, lod, None if tap is None else tap["mean"], cut)
+    var = blur(x * x, lod, None if tap is None else tap["square"], cut) - mean * mean
     std = torch.sqrt(torch.where(var < VAR_FLOOR, torch.full_like(var, VAR_FLOOR), var))
     return mean, std, var
 
@@ -114,16 +128,20 @@ def lod_maps(gaze, H, W, n_levels, alpha, width, distance, mode, dtype=torch.flo
     return [lod_map(gaze, (H >> l, W >> l), alpha, width, distance, mode, dtype, device) for l in range(n_levels - 1)]
 
 
-def stats_maps(x, filters, lods, n_levels, want_vars=False):
-    """metameric_loss.py:125-167: [mean h, std h, (mean, std) per band per level .., last lowpass]; h shares level 0's map"""
+def stats_maps(x, filters, lods, n_levels, want_vars=False, taps=None):
+    """metameric_loss.py:125-167: [mean h, std h, (mean, std) per band per level .., last lowpass]; h shares level 0's map.
+    taps: {pyramid level: dict(mean=[], square=[], cut=None or (k, y0, y1))}: the lists receive, per map of that level in the
+    library's order (h in front of level 0's bands), the chain of the map and the chain of its square (blur's chain_out); cut
+    is handed to every blur of that level."""
     h, bands, low = hvs_ref.pyramid(x, filters, n_levels)
+    taps = taps or {}
     out, variances = [], []
-    m, s, v = find_stats(h, lods[0])
+    m, s, v = find_stats(h, lods[0], taps.get(0))
     out += [m, s]
     variances.append(v)
-    for level, lod in zip(bands, lods):
+    for l, (level, lod) in enumerate(zip(bands, lods)):
         for b in level:
-            m, s, v = find_stats(b, lod)
+            m, s, v = find_stats(b, lod, taps.get(l))
             out += [m, s]
             variances.append(v)
     out.append(low)
@@ -131,8 +149,9 @@ def stats_maps(x, filters, lods, n_levels, want_vars=False):
 
 
 def fov_loss(image, target, filters, gaze=(0.5, 0.5), alpha=0.2, real_image_width=0.2, real_viewing_distance=0.7, n_pyramid_levels=5,
-             mode="quadratic", loss_type="L1", image_colorspace="RGB", return_maps=False, lods=None):
-    """MetamericLoss.__call__ (:204-271) with use_l2_foveal_loss=False: image, target [1,3,H,W]; autograd to image only"""
+             mode="quadratic", loss_type="L1", image_colorspace="RGB", return_maps=False, lods=None, taps=None):
+    """MetamericLoss.__call__ (:204-271) with use_l2_foveal_loss=False: image, target [1,3,H,W]; autograd to image only.
+    taps: stats_maps's, for the image's side"""
     hvs_ref.check_size(image.size(2), image.size(3), n_pyramid_levels)
     target = target.detach()
     if image_colorspace == "RGB":
@@ -140,7 +159,7 @@ def fov_loss(image, target, filters, gaze=(0.5, 0.5), alpha=0.2, real_image_widt
     if lods is None:
         lods = lod_maps(gaze, image.size(2), image.size(3), n_pyramid_levels, alpha, real_image_width, real_viewing_distance, mode,
                         image.dtype, image.device)
-    a = stats_maps(image, filters, lods, n_pyramid_levels)
+    a = stats_maps(image, filters, lods, n_pyramid_levels, taps=taps)
     with torch.no_grad():
         b = stats_maps(target, filters, lods, n_pyramid_levels)
     loss = 0.0
@@ -180,3 +199,9 @@ def undecided_sign_gradient(image, target, filters, lods, n_levels, threshold=hv
     g_full, = torch.autograd.grad(full, img, retain_graph=True)
     g_part, = torch.autograd.grad(part, img)
     return n, float(g_part.abs().max() / g_full.abs().max())
+
+
+def chain_gradients(tap, k):
+    """after backward(): [2, nmc, h_k, w_k] = the loss's gradient with respect to chain level k of a tapped pyramid level's maps,
+    the mean chain first, then the chain of the square, the maps in the library's order (csrc/hvs_fov.hip: g[k])"""
+    return torch.stack([torch.cat([chain[k].grad[0] for chain in tap[which]]) for which in ("mean", "square")])

@@ -176,7 +176,7 @@ def test_abi_names_declared_and_exported():
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fovraster.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(fr_[a-z_0-9A-Z]+)\s*\(", txt))
     lib = _native.load()
-    for n in ("fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward"):
+    for n in ("fr_hvs_fov_workspace_floats", "fr_hvs_fov_forward", "fr_hvs_fov_backward", "fr_hvs_fov_backward_plan"):
         assert n in declared and n in _native.EXPORTS and n not in _native.OPTIONAL_EXPORTS and hasattr(lib, n), n
     assert lib.fr_abi_version() == 12 == _native.ABI_VERSION
     assert "hvs_fov.hip" in open(os.path.join(ROOT, "fov-3dgs_amd", "csrc", "Makefile")).read()
@@ -195,7 +195,8 @@ def test_sizes_on_which_the_reference_raises_are_refused(H, W):
         [hvs_fov_ref.chain_sizes(H >> l, W >> l) for l in range(4)]  # the restatement refuses them too
 
 
-@pytest.mark.parametrize("H,W,levels", [(1088, 1920, 5), (32, 64, 5), (32, 32, 5), (64, 64, 5), (64, 96, 5), (96, 64, 5), (40, 56, 3)])
+@pytest.mark.parametrize("H,W,levels", [(1088, 1920, 5), (32, 64, 5), (32, 32, 5), (64, 64, 5), (64, 96, 5), (96, 64, 5), (40, 56, 3),
+                                        (136, 244, 2), (200, 344, 3), (392, 408, 3), (64, 64, 6)])  # ... and ref_hvs_fov_large.npz's
 def test_supported_sizes_and_their_layout(H, W, levels):
     st = _settings(H, W, levels)
     lv = _native_hvs_fov.layout(st)  # asserts that the Python layout and the library agree on the sizes
