@@ -86,3 +86,99 @@ def pack_bits(values, bits):
     v = np.asarray(values).astype(np.int64).reshape(-1)
     m = (v[:, None] >> np.arange(bits - 1, -1, -1)[None, :]) & 1
     return np.packbits(m.astype(bool).reshape(-1))
+
+
+# ---- the codebook step as csrc/vq.hip performs it, operation for operation (float32) ---------------------------------------------
+U = 2.0 ** -24
+TILE = 1024  # rows per counting-sort tile (VQ_TILE), and the width of k_vq_sum's / k_vq_select's one workgroup
+
+
+def fixed_order_sum(v):
+    """k_vq_sum: thread t adds elements t, t + 1024, ... in double, then the 512 ... 1 tree. -> the double (the kernel rounds it to float once)"""
+    v = np.asarray(v, np.float32).astype(np.float64)
+    pad = np.zeros((v.shape[0] + TILE - 1) // TILE * TILE)
+    pad[:v.shape[0]] = v
+    sh = np.zeros(TILE)
+    for stride in pad.reshape(-1, TILE):
+        sh = sh + stride
+    m = TILE // 2
+    while m >= 1:
+        sh[:m] = sh[:m] + sh[m:2 * m]
+        m //= 2
+    return sh[0]
+
+
+def sort_rows(ind, K):
+    """The stable counting sort: -> (perm int64 [n]: rows by code, ascending row position inside a code; seg int64 [K + 1])"""
+    ind = np.asarray(ind).astype(np.int64)
+    seg = np.concatenate([[0], np.cumsum(np.bincount(ind, minlength=K))])
+    return np.argsort(ind, kind="stable"), seg
+
+
+def emulate_update(x, w, ind, embed, cs, decay=DECAY, eps=EPS, perm=None, seg=None, defect=None):
+    """fr_vq_update in numpy float32, one rounding per operation in the kernels' order. x [n, D] and w [n] (or None) are the rows of
+    the call (already gathered through `rows`). perm / seg: another sort than sort_rows' and defect="ema" (decay and 1 - decay
+    exchanged in the cluster-size EMA) exist for the tests that show a judge rejecting a defective restatement.
+    -> dict(embed, cluster_size, embed_sum, batch, smoothed, wp), float32"""
+    f = np.float32
+    x, embed, cs = np.asarray(x, f), np.asarray(embed, f), np.asarray(cs, f)
+    n, K = x.shape[0], embed.shape[0]
+    decay, eps = f(decay), f(eps)
+    omd = f(1.0 - float(decay))
+    if perm is None:
+        perm, seg = sort_rows(ind, K)
+    if w is None:
+        wp = np.ones(n, f)
+    else:
+        w = np.asarray(w, f)
+        wp = (w * f(n)) / f(fixed_order_sum(w))
+    seg = np.minimum(np.asarray(seg, np.int64), n)
+    length = np.maximum(seg[1:] - seg[:-1], 0)
+    acc, bs = np.zeros(embed.shape, f), np.zeros(K, f)
+    for j in range(int(length.max())):  # the j-th member of every code that has one: acc = fl(acc + fl(w' x)), bs = fl(bs + w')
+        c = np.nonzero(length > j)[0]
+        i = perm[seg[c] + j]
+        acc[c] = acc[c] + wp[i][:, None] * x[i]
+        bs[c] = bs[c] + wp[i]
+    if defect == "ema":
+        new_cs = cs * omd + decay * bs
+    else:
+        new_cs = cs * decay + omd * bs
+    S = f(fixed_order_sum(new_cs))
+    k_eps = f(float(K) * float(eps))
+    with np.errstate(all="ignore"):  # (a state that sums to nothing divides by zero here as it does on the device)
+        smoothed = ((new_cs + eps) / (S + k_eps)) * S
+        new_embed = embed * decay + omd * (acc / smoothed[:, None])
+    for a in (wp, acc, bs, new_cs, smoothed, new_embed):
+        assert a.dtype == f
+    return dict(embed=new_embed, cluster_size=new_cs, embed_sum=acc, batch=bs, smoothed=smoothed, wp=wp)
+
+
+def update_bounds(x, w, ind, embed, cs, decay=DECAY, eps=EPS):
+    """First-order bounds of emulate_update's arithmetic against train_step's float64 values (derived, not measured; u = 2^-24, m_c the
+    members of code c, sums of magnitudes in float64). A sum of m terms, each a rounded product of a w' that itself carries two
+    roundings, added one at a time: (m - 1) + 1 + 2 = m + 2 roundings on sum w', one more for the product w' x.
+      batch         (m_c + 2) u sum w'
+      cluster_size  (1 - decay) bound(batch) + 3 u |cs_new|                         (two products and a sum)
+      embed_sum     E = (m_c + 3) u sum w' |x|
+      smoothed      relative: bound(cs) / (cs + eps) + 6 u                          (S carries the relative error of its terms at most)
+      embed         (1 - decay) / smoothed (E + |esum| rel(smoothed)) + 3 u (decay |e| + (1 - decay) |esum| / smoothed)
+    -> dict(batch [K], cluster_size [K], embed_sum [K, D], smoothed_rel [K], embed [K, D])"""
+    x, embed, cs = np.asarray(x, np.float64), np.asarray(embed, np.float64), np.asarray(cs, np.float64)
+    n, K = x.shape[0], embed.shape[0]
+    ind = np.asarray(ind).astype(np.int64)
+    wp = np.ones(n) if w is None else np.asarray(w, np.float64) * n / np.asarray(w, np.float64).sum()
+    m = np.bincount(ind, minlength=K)
+    sum_wp = np.bincount(ind, weights=wp, minlength=K)
+    batch = (m + 2) * U * sum_wp
+    new_cs = decay * cs + (1 - decay) * sum_wp
+    b_cs = (1 - decay) * batch + 3 * U * np.abs(new_cs)
+    mag, esum = np.zeros_like(embed), np.zeros_like(embed)
+    np.add.at(mag, ind, wp[:, None] * np.abs(x))
+    np.add.at(esum, ind, wp[:, None] * x)
+    E = (m + 3)[:, None] * U * mag
+    rel = b_cs / (new_cs + eps) + 6 * U
+    smoothed = (new_cs + eps) / (new_cs.sum() + K * eps) * new_cs.sum()
+    b_embed = ((1 - decay) / smoothed[:, None] * (E + np.abs(esum) * rel[:, None])
+               + 3 * U * (decay * np.abs(embed) + (1 - decay) * np.abs(esum) / smoothed[:, None]))
+    return dict(batch=batch, cluster_size=b_cs, embed_sum=E, smoothed_rel=rel, embed=b_embed)
