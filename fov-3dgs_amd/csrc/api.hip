@@ -282,6 +282,28 @@ static int validate_fov_keep(const fr_forward_args *a, const fr_foveation *fov, 
 	return FR_OK;
 }
 
+// The kept state a foveated backward pass is handed (`who`: the entry point, for the messages). full: fr_backward_fov, which wants the
+// state of a _full forward and has nothing to do without Gaussians; fr_backward_fov_appearance wants a plain keep state and answers
+// FR_OK for P == 0 (the caller's: the workspaces of such a state are not looked at). Each pass refuses the other's state.
+static int validate_fov_state(const fr_fov_state *st, const char *who, bool full)
+{
+	if (!st) { set_error("%s: state is null", who); return FR_ERR_INVALID; }
+	if (st->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", st->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
+	if ((st->variant & ~FR_FOV_STATE_FULL) != FR_VARIANT_FOV_PCHECK_OBB)
+	{ set_error("%s: state.variant is %d, not %d (fov_pcheck_obb): not the state of a state-keeping foveated forward", who, st->variant & ~FR_FOV_STATE_FULL, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
+	if (full && !(st->variant & FR_FOV_STATE_FULL))
+	{ set_error("%s: state.variant lacks FR_FOV_STATE_FULL: the state was not made by fr_forward_begin_fov_keep_full (its geometry workspace has no rows of moments)", who); return FR_ERR_INVALID; }
+	if (!full && (st->variant & FR_FOV_STATE_FULL))
+	{ set_error("%s: state.variant carries FR_FOV_STATE_FULL: the state was made by fr_forward_begin_fov_keep_full, whose rows of moments this pass would leave uncleared", who); return FR_ERR_INVALID; }
+	if (st->levels < 2 || st->levels > FR_FOV_LEVELS)
+	{ set_error("%s: state.levels is %d, not in 2..%d (levels 5 .. 8 would need a second row of sums)", who, st->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
+	if (st->P < 0 || (full && st->P == 0) || st->W <= 0 || st->H <= 0 || st->num_rendered < 0 || st->num_items < 0
+		|| (int64_t)st->num_items > 4 * (int64_t)((st->W + FR_TILE - 1) / FR_TILE) * ((st->H + FR_TILE - 1) / FR_TILE))
+	{ set_error("%s: state holds bad sizes (P=%d W=%d H=%d num_rendered=%d num_items=%d)", who, st->P, st->W, st->H, st->num_rendered, st->num_items); return FR_ERR_INVALID; }
+	if (st->P > 0 && (!st->geometry || !st->image || (st->num_rendered > 0 && !st->binning))) { set_error("%s: state.geometry / image / binning is null", who); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
 // keep: 0 = the inference frame, 1 = the state-keeping forward, 2 = the same for the full backward pass (fr_forward_begin_fov_keep_full)
 static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, int keep, fr_frame **out)
 {
@@ -858,17 +880,9 @@ int fr_backward_fov_appearance(const fr_backward_fov_args *a)
 	if (!a) { set_error("null args"); return FR_ERR_INVALID; }
 	if (a->size < sizeof(fr_backward_fov_args)) { set_error("fr_backward_fov_args.size is %u, expected at least %u", a->size, (unsigned)sizeof(fr_backward_fov_args)); return FR_ERR_INVALID; }
 	const fr_fov_state *st = a->state;
-	if (!st) { set_error("backward_fov_appearance: state is null"); return FR_ERR_INVALID; }
-	if (st->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", st->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
-	if (st->variant != FR_VARIANT_FOV_PCHECK_OBB)
-	{ set_error("backward_fov_appearance: state.variant is %d, not %d (fov_pcheck_obb): not the state of a state-keeping foveated forward", st->variant, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
-	if (st->levels < 2 || st->levels > FR_FOV_LEVELS)
-	{ set_error("backward_fov_appearance: state.levels is %d, not in 2..%d (levels 5 .. 8 would need a second row of sums)", st->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
-	if (st->P < 0 || st->W <= 0 || st->H <= 0 || st->num_rendered < 0 || st->num_items < 0
-		|| (int64_t)st->num_items > 4 * (int64_t)((st->W + FR_TILE - 1) / FR_TILE) * ((st->H + FR_TILE - 1) / FR_TILE))
-	{ set_error("backward_fov_appearance: state holds bad sizes (P=%d W=%d H=%d num_rendered=%d num_items=%d)", st->P, st->W, st->H, st->num_rendered, st->num_items); return FR_ERR_INVALID; }
+	const int rc = validate_fov_state(st, "backward_fov_appearance", false);
+	if (rc) return rc;
 	if (st->P == 0) return FR_OK;
-	if (!st->geometry || !st->image || (st->num_rendered > 0 && !st->binning)) { set_error("backward_fov_appearance: state.geometry / image / binning is null"); return FR_ERR_INVALID; }
 	if (!a->dL_dpix) { set_error("backward_fov_appearance: dL_dpix is null"); return FR_ERR_INVALID; }
 	if (!a->background) { set_error("backward_fov_appearance: background is null"); return FR_ERR_INVALID; }
 	if (!a->dL_dopacities) { set_error("backward_fov_appearance: dL_dopacities is null"); return FR_ERR_INVALID; }
@@ -881,18 +895,8 @@ int fr_backward_fov(const fr_backward_fov_full_args *a)
 	if (!a) { set_error("null arguments"); return FR_ERR_INVALID; }
 	if (a->size < sizeof(fr_backward_fov_full_args)) { set_error("fr_backward_fov_full_args.size is %u, expected at least %u", a->size, (unsigned)sizeof(fr_backward_fov_full_args)); return FR_ERR_INVALID; }
 	const fr_fov_state *st = a->state;
-	if (!st) { set_error("backward_fov: state is null"); return FR_ERR_INVALID; }
-	if (st->size < sizeof(fr_fov_state)) { set_error("fr_fov_state.size is %u, expected at least %u", st->size, (unsigned)sizeof(fr_fov_state)); return FR_ERR_INVALID; }
-	if ((st->variant & ~FR_FOV_STATE_FULL) != FR_VARIANT_FOV_PCHECK_OBB)
-	{ set_error("backward_fov: state.variant is %d, not %d (fov_pcheck_obb): not the state of a state-keeping foveated forward", st->variant & ~FR_FOV_STATE_FULL, FR_VARIANT_FOV_PCHECK_OBB); return FR_ERR_INVALID; }
-	if (!(st->variant & FR_FOV_STATE_FULL))
-	{ set_error("backward_fov: state.variant lacks FR_FOV_STATE_FULL: the state was not made by fr_forward_begin_fov_keep_full (its geometry workspace has no rows of moments)"); return FR_ERR_INVALID; }
-	if (st->levels < 2 || st->levels > FR_FOV_LEVELS)
-	{ set_error("backward_fov: state.levels is %d, not in 2..%d (levels 5 .. 8 would need a second row of sums)", st->levels, FR_FOV_LEVELS); return FR_ERR_INVALID; }
-	if (st->P <= 0 || st->W <= 0 || st->H <= 0 || st->num_rendered < 0 || st->num_items < 0
-		|| st->num_items > 4 * ((st->W + FR_TILE - 1) / FR_TILE) * ((st->H + FR_TILE - 1) / FR_TILE))
-	{ set_error("backward_fov: state holds bad sizes (P=%d W=%d H=%d num_rendered=%d num_items=%d)", st->P, st->W, st->H, st->num_rendered, st->num_items); return FR_ERR_INVALID; }
-	if (!st->geometry || !st->image || (st->num_rendered > 0 && !st->binning)) { set_error("backward_fov: state.geometry / image / binning is null"); return FR_ERR_INVALID; }
+	const int rc = validate_fov_state(st, "backward_fov", true);
+	if (rc) return rc;
 	if (a->P != st->P) { set_error("backward_fov: P is %d, the state's %d", a->P, st->P); return FR_ERR_INVALID; }
 	if (a->M < 1 || a->M > 16 || a->sh_degree < 0 || a->sh_degree > 3 || (a->sh_degree + 1) * (a->sh_degree + 1) > a->M)
 	{ set_error("backward_fov: M is %d and sh_degree %d (1 <= (sh_degree + 1)^2 <= M <= 16)", a->M, a->sh_degree); return FR_ERR_INVALID; }

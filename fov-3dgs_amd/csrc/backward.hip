@@ -807,6 +807,35 @@ __global__ void __launch_bounds__(256) k_fill_zero(const FillArgs a)
 		if (blockIdx.x == 0 && threadIdx.x < tail) a.p[t][4 * quads + threadIdx.x] = 0.0f;
 	}
 }
+// The dense outputs of a backward call cleared by ONE k_fill_zero on `stream` (seven fill commands in a row ran at 2.7 TB/s beside
+// k_render_bwd, the small ones at 1 TB/s, and outlasted it by 50 us). Null and empty entries are skipped; a tensor that is not 16-byte
+// aligned -- what no allocator hands out -- or one more than the table holds is cleared by hipMemsetAsync instead.
+// grid_words: the grid is the one a tensor of that many words asks for, at most FR_FILL_BLOCKS; 0: the widest tensor of the table.
+// what: the launch's name in an error message.
+struct Fill { void *p; size_t words; };
+static int fill_outputs(const Fill *fills, const int n, size_t grid_words, hipStream_t stream, const char *what, const int debug)
+{
+	FillArgs fa; fa.n = 0;
+	size_t widest = 0;
+	for (int i = 0; i < n; i++)
+	{
+		const Fill &f = fills[i];
+		if (!f.p || !f.words) continue;
+		if (((uintptr_t)f.p & 15) != 0 || fa.n == FR_FILL_MAX)
+		{
+			const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
+			if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+			continue;
+		}
+		fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
+		if (f.words > widest) widest = f.words;
+	}
+	if (!fa.n) return FR_OK;
+	if (!grid_words) grid_words = widest;
+	const size_t blocks = ((grid_words + 3) / 4 + 255) / 256;
+	hipLaunchKernelGGL(k_fill_zero, dim3((unsigned)(blocks < FR_FILL_BLOCKS ? blocks : FR_FILL_BLOCKS)), dim3(256), 0, stream, fa);
+	return check_launch(what, stream, debug);
+}
 
 // The narrow tensors' share of the fill (SmallSet): the 32-row groups WITHOUT a visible Gaussian. One wave per 64 rows (two groups):
 // their radii as one coalesced load, a ballot, and the zeros of an empty group as 16-byte (both groups) or 4-byte stores.
@@ -1058,6 +1087,15 @@ __global__ void __launch_bounds__(256) k_appearance_bwd(const BwdAppArgs a)
 	}
 }
 
+// the optional diagnostic of a tile pass (blend_pairs: [T] counters its kernel adds to) starts from zeros
+static int clear_blend_pairs(uint32_t *pairs, const int T, hipStream_t stream)
+{
+	if (pairs == nullptr) return FR_OK;
+	const hipError_t e = hipMemsetAsync(pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
+	if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
+	return FR_OK;
+}
+
 static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, const ImageWS &img, const BinWS &bin, int gx, int T, hipStream_t stream,
 	bool lean = false)
 {
@@ -1067,11 +1105,8 @@ static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, cons
 	r.bg = a->background; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.dL_dpix = a->dL_dpix;
 	r.acc = (float *)geom.acc;
 	r.pairs = a->blend_pairs;
-	if (r.pairs != nullptr)
-	{
-		const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
-		if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-	}
+	const int rcp = clear_blend_pairs(r.pairs, T, stream);
+	if (rcp) return rcp;
 	if (lean)
 	{
 		if (a->variant == FR_VARIANT_ORIGINAL)
@@ -1087,8 +1122,6 @@ static int launch_render_bwd(const fr_backward_args *a, const GeomWS &geom, cons
 	return check_launch("render_bwd", stream, a->debug);
 }
 
-// the dense gradient tensors of a backward call cleared by ONE kernel on stream `fs` (seven fill commands in a row ran at 2.7 TB/s
-// beside k_render_bwd, the small ones at 1 TB/s, and outlasted it by 50 us); tensors are 16-byte aligned and their sizes multiples of 4
 // the narrow tensors of a dense backward call (SmallSet): written in whole lines by k_preprocess_bwd + k_fill_groups instead of fill + rows
 static SmallSet small_set(const fr_backward_args *a)
 {
@@ -1117,42 +1150,21 @@ int launch_gradient_fill(const fr_backward_args *a, hipStream_t fs, bool events,
 	const bool have_sh = a->colors_precomp == nullptr && a->shs != nullptr;
 	const size_t P = (size_t)a->P;
 	const size_t m0 = have_sh ? (a->shs_rest ? 1 : (size_t)a->M) : 0;
-	struct { void *p; size_t bytes; } fills[] = {
-		{ a->dL_dmean3D, 12 * P }, { a->dL_dmean2D, 12 * P }, { a->dL_dopacity, 4 * P }, { a->dL_dscale, 12 * P }, { a->dL_drot, 16 * P },
-		{ a->dL_dsh, 12 * m0 * P }, { a->dL_dsh_rest, have_sh && a->shs_rest ? 12 * ((size_t)a->M - 1) * P : 0 },
-		{ a->dL_dcolor, 12 * P }, { a->dL_dconic, 16 * P }, { a->dL_dcov3D, 24 * P } };
-	FillArgs fa; fa.n = 0;
-	for (auto &f : fills)
-		if (f.p && f.bytes && !narrow(f.p))
-		{
-			if (((uintptr_t)f.p & 15) != 0 || fa.n == FR_FILL_MAX)
-			{
-				const hipError_t e = hipMemsetAsync(f.p, 0, f.bytes, fs);
-				if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-				continue;
-			}
-			fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.bytes / 4; fa.n++;
-		}
-	if (fa.n || ss.n)
+	Fill fills[] = { { a->dL_dmean3D, 3 * P }, { a->dL_dmean2D, 3 * P }, { a->dL_dopacity, P }, { a->dL_dscale, 3 * P }, { a->dL_drot, 4 * P },
+		{ a->dL_dsh, 3 * m0 * P }, { a->dL_dsh_rest, have_sh && a->shs_rest ? 3 * ((size_t)a->M - 1) * P : 0 },
+		{ a->dL_dcolor, 3 * P }, { a->dL_dconic, 4 * P }, { a->dL_dcov3D, 6 * P } };
+	for (Fill &f : fills) if (narrow(f.p)) f.words = 0; // (k_fill_groups' and k_preprocess_bwd's)
+	// (optional events 3 / 4: around the fill kernels, on the stream they run on)
+	if (events && a->stage_events && a->stage_events[3]) (void)hipEventRecord((hipEvent_t)a->stage_events[3], fs);
+	int rcf = fill_outputs(fills, (int)(sizeof(fills) / sizeof(fills[0])), (size_t)FR_FILL_BLOCKS * 1024, fs, "fill_zero", a->debug); // (FR_FILL_BLOCKS blocks)
+	if (!rcf && ss.n)
 	{
-		// (optional events 3 / 4: around the fill kernels, on the stream they run on)
-		if (events && a->stage_events && a->stage_events[3]) (void)hipEventRecord((hipEvent_t)a->stage_events[3], fs);
-		int rcf = FR_OK;
-		if (fa.n)
-		{
-			hipLaunchKernelGGL(k_fill_zero, dim3(FR_FILL_BLOCKS), dim3(256), 0, fs, fa);
-			rcf = check_launch("fill_zero", fs, a->debug);
-		}
-		if (!rcf && ss.n)
-		{
-			const int nblk = (a->P + 63) / 64;
-			hipLaunchKernelGGL(k_fill_groups, dim3((unsigned)min((nblk + 3) / 4, 8192)), dim3(256), 0, fs, a->P, a->radii, ss);
-			rcf = check_launch("fill_groups", fs, a->debug);
-		}
-		if (events && a->stage_events && a->stage_events[4]) (void)hipEventRecord((hipEvent_t)a->stage_events[4], fs);
-		if (rcf) return rcf;
+		const int nblk = (a->P + 63) / 64;
+		hipLaunchKernelGGL(k_fill_groups, dim3((unsigned)min((nblk + 3) / 4, 8192)), dim3(256), 0, fs, a->P, a->radii, ss);
+		rcf = check_launch("fill_groups", fs, a->debug);
 	}
-	return FR_OK;
+	if (events && a->stage_events && a->stage_events[4]) (void)hipEventRecord((hipEvent_t)a->stage_events[4], fs);
+	return rcf;
 }
 
 int launch_backward(const fr_backward_args *a)
@@ -1265,28 +1277,10 @@ int launch_backward_appearance(const fr_backward_args *a)
 	if (!a->row_sparse && !a->outputs_zeroed)
 	{
 		const size_t P = (size_t)a->P;
-		struct { void *p; size_t words; } fills[] = { { a->dL_dopacity, P }, { a->dL_dsh, 3 * P }, { a->dL_dcolor, 3 * P } };
-		FillArgs fa; fa.n = 0;
+		const Fill fills[] = { { a->dL_dopacity, P }, { a->dL_dsh, 3 * P }, { a->dL_dcolor, 3 * P } };
 		mark(3);
-		for (auto &f : fills)
-			if (f.p)
-			{
-				if (((uintptr_t)f.p & 15) != 0)
-				{
-					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
-					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-					continue;
-				}
-				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
-			}
-		if (fa.n)
-		{
-			const size_t quads = (3 * P + 3) / 4;
-			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
-			hipLaunchKernelGGL(k_fill_zero, dim3(blocks), dim3(256), 0, stream, fa);
-			const int rcf = check_launch("fill_zero (appearance)", stream, a->debug);
-			if (rcf) return rcf;
-		}
+		const int rcf = fill_outputs(fills, 3, 3 * P, stream, "fill_zero (appearance)", a->debug);
+		if (rcf) return rcf;
 		mark(4);
 	}
 	mark(0);
@@ -1328,34 +1322,43 @@ struct BwdFovAppArgs {
 	int L;
 };
 
+// The rule above for visible-list item i, the ONE place it is written down: both per-Gaussian kernels of the foveated renderer are this
+// function (k_fov_full_bwd goes on with the chain rule). -> the item's Gaussian, or -1 for an item that landed in no tile (nothing read,
+// nothing stored); col: the colour sums of the item's levels added up, clamped channels left out -- what the rest coefficients and the
+// view direction receive in the full pass (the appearance pass has no use for it).
+__device__ __forceinline__ int fov_level_grads(const BwdFovAppArgs &a, const int i, float (&col)[3])
+{
+	const uint32_t lr = a.lrange[i];
+	if (lr == FR_ITEM_NONE) return -1;
+	const int lo = (int)(lr & 0xffu), hi = (int)((lr >> 8) & 0xffu);
+	const int idx = (int)a.vis_list[i];
+	col[0] = col[1] = col[2] = 0.0f;
+#pragma unroll
+	for (int l = 0; l < FR_FOV_LEVELS; l++)
+	{
+		if (l >= a.L) break;
+		const float4 s = a.acc[4 * (size_t)i + l];
+		a.acc[4 * (size_t)i + l] = make_float4(0.f, 0.f, 0.f, 0.f);
+		const bool used = l >= lo && l <= hi;
+		const float4 c = used ? a.lvl[4 * (size_t)i + l] : make_float4(0.f, 0.f, 0.f, 0.f);
+		const float o0 = c.x > 0.0f ? s.x : 0.0f, o1 = c.y > 0.0f ? s.y : 0.0f, o2 = c.z > 0.0f ? s.z : 0.0f;
+		col[0] += o0; col[1] += o1; col[2] += o2;
+		const size_t o = (size_t)idx * (size_t)a.L + l;
+		FR_ST(a.dL_dopacities + o, s.w);
+		FR_ST(a.dL_dshs_dcs + 3 * o, FR_SH_C0 * o0); FR_ST(a.dL_dshs_dcs + 3 * o + 1, FR_SH_C0 * o1); FR_ST(a.dL_dshs_dcs + 3 * o + 2, FR_SH_C0 * o2);
+		if (a.dL_dlevel_colours != nullptr)
+		{
+			FR_ST(a.dL_dlevel_colours + 3 * o, s.x); FR_ST(a.dL_dlevel_colours + 3 * o + 1, s.y); FR_ST(a.dL_dlevel_colours + 3 * o + 2, s.z);
+		}
+	}
+	return idx;
+}
+
 __global__ void __launch_bounds__(256) k_fov_appearance_bwd(const BwdFovAppArgs a)
 {
 	const int V = (int)*a.vis_count;
-	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x))
-	{
-		const uint32_t lr = a.lrange[i];
-		if (lr == FR_ITEM_NONE) continue;
-		const int lo = (int)(lr & 0xffu), hi = (int)((lr >> 8) & 0xffu);
-		const size_t g = (size_t)a.vis_list[i];
-#pragma unroll
-		for (int l = 0; l < FR_FOV_LEVELS; l++)
-		{
-			if (l >= a.L) break;
-			const float4 s = a.acc[4 * (size_t)i + l];
-			a.acc[4 * (size_t)i + l] = make_float4(0.f, 0.f, 0.f, 0.f);
-			const bool used = l >= lo && l <= hi;
-			const float4 c = used ? a.lvl[4 * (size_t)i + l] : make_float4(0.f, 0.f, 0.f, 0.f);
-			const size_t o = g * (size_t)a.L + l;
-			FR_ST(a.dL_dopacities + o, s.w);
-			FR_ST(a.dL_dshs_dcs + 3 * o, c.x > 0.0f ? FR_SH_C0 * s.x : 0.0f);
-			FR_ST(a.dL_dshs_dcs + 3 * o + 1, c.y > 0.0f ? FR_SH_C0 * s.y : 0.0f);
-			FR_ST(a.dL_dshs_dcs + 3 * o + 2, c.z > 0.0f ? FR_SH_C0 * s.z : 0.0f);
-			if (a.dL_dlevel_colours != nullptr)
-			{
-				FR_ST(a.dL_dlevel_colours + 3 * o, s.x); FR_ST(a.dL_dlevel_colours + 3 * o + 1, s.y); FR_ST(a.dL_dlevel_colours + 3 * o + 2, s.z);
-			}
-		}
-	}
+	float col[3];
+	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x)) (void)fov_level_grads(a, i, col);
 }
 
 // per: float4s a row (4: the rows of sums; 2: the rows of moments of the full backward pass)
@@ -1375,78 +1378,10 @@ int launch_fov_keep_clear(FwdCtx &c)
 	return check_launch("clear_item_rows (moments)", c.stream, c.a->debug);
 }
 
-// One k_fill_zero over the dense outputs in front of the tile pass (as fr_backward_appearance: they are 28 L bytes a Gaussian), the
-// tile pass over the forward's work items, the per-Gaussian pass. Everything on the caller's stream, no synchronisation.
-int launch_backward_fov_appearance(const fr_backward_fov_args *a)
-{
-	const fr_fov_state *st = a->state;
-	hipStream_t stream = (hipStream_t)a->stream;
-	const int gx = (st->W + FR_TILE - 1) / FR_TILE, gy = (st->H + FR_TILE - 1) / FR_TILE, T = gx * gy;
-	const size_t P = (size_t)st->P;
-	const int L = st->levels;
-	GeomWS geom = carve_geom(FR_VARIANT_FOV_PCHECK_OBB, P, (char *)st->geometry, L);
-	ImageWS img = carve_image(FR_VARIANT_FOV_PCHECK_OBB, st->W, st->H, (char *)st->image);
-	BinWS bin = carve_bin(st->num_rendered, (char *)st->binning);
-	const FovKeepGeom kg = carve_fov_keep_geom(P, (char *)st->geometry, L);
-	const FovKeepImage ki = carve_fov_keep_image(st->W, st->H, (char *)st->image);
-	auto mark = [&](int i) { if (a->stage_events && a->stage_events[i]) (void)hipEventRecord((hipEvent_t)a->stage_events[i], stream); };
-	{
-		struct { void *p; size_t words; } fills[] = { { a->dL_dopacities, P * L }, { a->dL_dshs_dcs, 3 * P * L }, { a->dL_dlevel_colours, 3 * P * L } };
-		FillArgs fa; fa.n = 0;
-		for (auto &f : fills)
-			if (f.p)
-			{
-				if (((uintptr_t)f.p & 15) != 0)
-				{
-					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
-					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-					continue;
-				}
-				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
-			}
-		if (fa.n)
-		{
-			const size_t quads = (3 * P * L + 3) / 4;
-			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
-			hipLaunchKernelGGL(k_fill_zero, dim3(blocks), dim3(256), 0, stream, fa);
-			const int rcf = check_launch("fill_zero (fov appearance)", stream, a->debug);
-			if (rcf) return rcf;
-		}
-	}
-	mark(0);
-	if (st->num_rendered > 0 && st->num_items > 0)
-	{
-		BwdFovArgs r;
-		r.W = st->W; r.H = st->H; r.gx = gx; r.ranges = img.ranges; r.render_items = img.render_items; r.n_items = (uint32_t)st->num_items;
-		r.point_list = bin.point_list; r.rec = geom.rec;
-		r.bg = a->background; r.final_T = ki.final_T; r.n_contrib = ki.n_contrib; r.dL_dpix = a->dL_dpix;
-		r.acc = (float *)kg.acc;
-		r.pairs = a->blend_pairs;
-		r.lvl = geom.lvl; r.tile_lv = img.tile_lv; r.T = T; r.start_blend = st->start_blend; r.blend_width = st->blend_width;
-		if (r.pairs != nullptr)
-		{
-			const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
-			if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-		}
-		hipLaunchKernelGGL(k_render_bwd_fov, dim3(r.n_items), dim3(64), 0, stream, r);
-		const int rc0 = check_launch("render_bwd_fov", stream, a->debug);
-		if (rc0) return rc0;
-	}
-	mark(1);
-	BwdFovAppArgs p;
-	p.acc = kg.acc; p.lvl = geom.lvl; p.vis_list = geom.vis_list; p.vis_count = geom.slab_ctr + 1; p.lrange = geom.lrange;
-	p.dL_dopacities = a->dL_dopacities; p.dL_dshs_dcs = a->dL_dshs_dcs; p.dL_dlevel_colours = a->dL_dlevel_colours; p.L = L;
-	const int pblocks = (int)((P + 255) / 256);
-	hipLaunchKernelGGL(k_fov_appearance_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
-	const int rc2 = check_launch("fov_appearance_bwd", stream, a->debug);
-	mark(2);
-	return rc2;
-}
-
 // ---- foveated full pass (fr_backward_fov) ----------------------------------------------------------------------------------------
-// Per visible-list item: the level quarters of its row of sums become dL/dopacities, dL/dshs_dcs and dL/dlevel_colours exactly as
-// k_fov_appearance_bwd forms them (same clamp rule: a stored level colour of 0 is a clamped channel); the colour sums of the levels
-// of the item's level range, clamped channels left out, are added up -- every level's colour is the SAME rest-SH part plus its own DC
+// Per visible-list item: the level quarters of its row of sums become dL/dopacities, dL/dshs_dcs and dL/dlevel_colours by the code
+// k_fov_appearance_bwd forms them with (fov_level_grads), which hands back the colour sums of the levels of the item's level range,
+// clamped channels left out, added up -- every level's colour is the SAME rest-SH part plus its own DC
 // term, so that sum is what the rest coefficients and the view direction receive (backward.cu:20-139); the five moments of the item's
 // second row give dL/dmean2D and dL/dconic (the opacities are in them already); and preprocess_bwd_one<true> runs k_preprocess_bwd's
 // chain rule on those. A foveated frame keeps no 64-byte row of (xyz | scale | rotation | 3D covariance) per item (GeomWS::cov3D is
@@ -1454,42 +1389,19 @@ int launch_backward_fov_appearance(const fr_backward_fov_args *a)
 // forms it. Both rows of sums are cleared again. Plain stores of the visible rows over ONE fill of all outputs (launch below).
 struct BwdFovFullArgs {
 	BwdPreArgs pre;            // camera, model tensors, the chain rule's outputs (what preprocess_bwd_one reads of it)
-	float4 *acc, *mom;
-	const float4 *lvl;
-	float *dL_dopacities, *dL_dshs_dcs, *dL_dlevel_colours;
-	int L;
+	BwdFovAppArgs lv;          // the level rule's: sums, level rows, visible list, per-level outputs
+	float4 *mom;
 };
 
 __global__ void __launch_bounds__(256) k_fov_full_bwd(const BwdFovFullArgs a)
 {
-	const int V = (int)*a.pre.vis_count;
+	const int V = (int)*a.lv.vis_count;
 	for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < V; i += (int)(gridDim.x * blockDim.x))
 	{
-		const uint32_t lr = a.pre.lrange[i];
-		if (lr == FR_ITEM_NONE) continue;
-		const int lo = (int)(lr & 0xffu), hi = (int)((lr >> 8) & 0xffu);
-		const int idx = (int)a.pre.vis_list[i];
-		const size_t g = (size_t)idx;
 		FovSums fs;
-		fs.col[0] = fs.col[1] = fs.col[2] = 0.0f;
-#pragma unroll
-		for (int l = 0; l < FR_FOV_LEVELS; l++)
-		{
-			if (l >= a.L) break;
-			const float4 s = a.acc[4 * (size_t)i + l];
-			a.acc[4 * (size_t)i + l] = make_float4(0.f, 0.f, 0.f, 0.f);
-			const bool used = l >= lo && l <= hi;
-			const float4 c = used ? a.lvl[4 * (size_t)i + l] : make_float4(0.f, 0.f, 0.f, 0.f);
-			const float o0 = c.x > 0.0f ? s.x : 0.0f, o1 = c.y > 0.0f ? s.y : 0.0f, o2 = c.z > 0.0f ? s.z : 0.0f;
-			fs.col[0] += o0; fs.col[1] += o1; fs.col[2] += o2;
-			const size_t o = g * (size_t)a.L + l;
-			FR_ST(a.dL_dopacities + o, s.w);
-			FR_ST(a.dL_dshs_dcs + 3 * o, FR_SH_C0 * o0); FR_ST(a.dL_dshs_dcs + 3 * o + 1, FR_SH_C0 * o1); FR_ST(a.dL_dshs_dcs + 3 * o + 2, FR_SH_C0 * o2);
-			if (a.dL_dlevel_colours != nullptr)
-			{
-				FR_ST(a.dL_dlevel_colours + 3 * o, s.x); FR_ST(a.dL_dlevel_colours + 3 * o + 1, s.y); FR_ST(a.dL_dlevel_colours + 3 * o + 2, s.z);
-			}
-		}
+		const int idx = fov_level_grads(a.lv, i, fs.col);
+		if (idx < 0) continue;
+		const size_t g = (size_t)idx;
 		const float4 m0 = a.mom[2 * (size_t)i], m1 = a.mom[2 * (size_t)i + 1];
 		a.mom[2 * (size_t)i] = a.mom[2 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
 		fs.m10 = m0.x; fs.m01 = m0.y; fs.m20 = m0.z; fs.m11 = m0.w; fs.m02 = m1.x;
@@ -1516,48 +1428,41 @@ __global__ void __launch_bounds__(256) k_fov_full_bwd(const BwdFovFullArgs a)
 	}
 }
 
-int launch_backward_fov_full(const fr_backward_fov_full_args *a)
+// Both foveated passes as ONE launcher: one k_fill_zero over the dense outputs in front of the tile pass (as fr_backward_appearance:
+// the appearance pass's are 28 L bytes a Gaussian, the grid sized by the colours; the full pass's widest, the rest coefficients, is 180
+// bytes a Gaussian and sizes its grid), the tile pass over the forward's work items, the per-Gaussian pass. Everything on the caller's
+// stream, no synchronisation. The passes differ in four places, each marked `full`: six more tensors to clear, the rows of moments, the
+// two kernels, the chain rule's arguments.
+struct FovBwdCall {
+	fr_backward_fov_args a;                 // what the two entry points' arguments have in common
+	const fr_backward_fov_full_args *full;  // fr_backward_fov's; null: the appearance pass
+};
+
+static int launch_backward_fov(const FovBwdCall &c)
 {
-	const fr_fov_state *st = a->state;
-	hipStream_t stream = (hipStream_t)a->stream;
+	const fr_backward_fov_args &a = c.a;
+	const fr_backward_fov_full_args *full = c.full;
+	const fr_fov_state *st = a.state;
+	hipStream_t stream = (hipStream_t)a.stream;
 	const int gx = (st->W + FR_TILE - 1) / FR_TILE, gy = (st->H + FR_TILE - 1) / FR_TILE, T = gx * gy;
 	const size_t P = (size_t)st->P;
 	const int L = st->levels;
 	GeomWS geom = carve_geom(FR_VARIANT_FOV_PCHECK_OBB, P, (char *)st->geometry, L);
 	ImageWS img = carve_image(FR_VARIANT_FOV_PCHECK_OBB, st->W, st->H, (char *)st->image);
 	BinWS bin = carve_bin(st->num_rendered, (char *)st->binning);
-	const FovFullGeom fg = carve_fov_full_geom(P, (char *)st->geometry, L);
+	float4 *acc = carve_fov_keep_geom(P, (char *)st->geometry, L).acc;
+	float4 *mom = full ? carve_fov_full_geom(P, (char *)st->geometry, L).mom : nullptr;
 	const FovKeepImage ki = carve_fov_keep_image(st->W, st->H, (char *)st->image);
-	auto mark = [&](int i) { if (a->stage_events && a->stage_events[i]) (void)hipEventRecord((hipEvent_t)a->stage_events[i], stream); };
-	const size_t nrest = a->M > 1 ? 3 * (size_t)(a->M - 1) : 0;
+	auto mark = [&](int i) { if (a.stage_events && a.stage_events[i]) (void)hipEventRecord((hipEvent_t)a.stage_events[i], stream); };
 	{
-		// one fill over every output (the widest, the rest coefficients, is 180 bytes a Gaussian; the grid is sized by it)
-		struct { void *p; size_t words; } fills[] = { { a->dL_dopacities, P * L }, { a->dL_dshs_dcs, 3 * P * L }, { a->dL_dlevel_colours, 3 * P * L },
-			{ a->dL_dshs_rest, nrest * P }, { a->dL_dmeans3D, 3 * P }, { a->dL_dscales, 3 * P }, { a->dL_drotations, 4 * P }, { a->dL_dmeans2D, 3 * P },
-			{ a->dL_dconic, 4 * P } };
-		FillArgs fa; fa.n = 0;
-		size_t widest = 0;
-		for (auto &f : fills)
-			if (f.p && f.words)
-			{
-				if (((uintptr_t)f.p & 15) != 0)
-				{
-					const hipError_t e = hipMemsetAsync(f.p, 0, 4 * f.words, stream);
-					if (e != hipSuccess) { set_error("hipMemsetAsync(gradient): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-					continue;
-				}
-				fa.p[fa.n] = (float *)f.p; fa.words[fa.n] = f.words; fa.n++;
-				if (f.words > widest) widest = f.words;
-			}
-		static_assert(FR_FILL_MAX >= 9, "the full foveated pass clears nine tensors with one launch");
-		if (fa.n)
-		{
-			const size_t quads = (widest + 3) / 4;
-			const unsigned blocks = (unsigned)((quads + 255) / 256 < FR_FILL_BLOCKS ? (quads + 255) / 256 : FR_FILL_BLOCKS);
-			hipLaunchKernelGGL(k_fill_zero, dim3(blocks ? blocks : 1), dim3(256), 0, stream, fa);
-			const int rcf = check_launch("fill_zero (fov full)", stream, a->debug);
-			if (rcf) return rcf;
-		}
+		Fill fills[9] = { { a.dL_dopacities, P * L }, { a.dL_dshs_dcs, 3 * P * L }, { a.dL_dlevel_colours, 3 * P * L } };
+		int nf = 3;
+		if (full)
+			for (const Fill &f : { Fill{ full->dL_dshs_rest, full->M > 1 ? 3 * (size_t)(full->M - 1) * P : 0 }, Fill{ full->dL_dmeans3D, 3 * P },
+				Fill{ full->dL_dscales, 3 * P }, Fill{ full->dL_drotations, 4 * P }, Fill{ full->dL_dmeans2D, 3 * P }, Fill{ full->dL_dconic, 4 * P } })
+				fills[nf++] = f;
+		const int rcf = fill_outputs(fills, nf, full ? 0 : 3 * P * L, stream, full ? "fill_zero (fov full)" : "fill_zero (fov appearance)", a.debug);
+		if (rcf) return rcf;
 	}
 	mark(0);
 	if (st->num_rendered > 0 && st->num_items > 0)
@@ -1565,39 +1470,49 @@ int launch_backward_fov_full(const fr_backward_fov_full_args *a)
 		BwdFovArgs r;
 		r.W = st->W; r.H = st->H; r.gx = gx; r.ranges = img.ranges; r.render_items = img.render_items; r.n_items = (uint32_t)st->num_items;
 		r.point_list = bin.point_list; r.rec = geom.rec;
-		r.bg = a->background; r.final_T = ki.final_T; r.n_contrib = ki.n_contrib; r.dL_dpix = a->dL_dpix;
-		r.acc = (float *)fg.acc; r.mom = (float *)fg.mom;
-		r.pairs = a->blend_pairs;
+		r.bg = a.background; r.final_T = ki.final_T; r.n_contrib = ki.n_contrib; r.dL_dpix = a.dL_dpix;
+		r.acc = (float *)acc; r.mom = (float *)mom;
+		r.pairs = a.blend_pairs;
 		r.lvl = geom.lvl; r.tile_lv = img.tile_lv; r.T = T; r.start_blend = st->start_blend; r.blend_width = st->blend_width;
-		if (r.pairs != nullptr)
-		{
-			const hipError_t e = hipMemsetAsync(r.pairs, 0, sizeof(uint32_t) * (size_t)T, stream);
-			if (e != hipSuccess) { set_error("hipMemsetAsync(blend_pairs): %s", hipGetErrorString(e)); return FR_ERR_HIP; }
-		}
-		hipLaunchKernelGGL(k_render_bwd_fov_full, dim3(r.n_items), dim3(64), 0, stream, r);
-		const int rc0 = check_launch("render_bwd_fov_full", stream, a->debug);
+		const int rcp = clear_blend_pairs(r.pairs, T, stream);
+		if (rcp) return rcp;
+		if (full) hipLaunchKernelGGL(k_render_bwd_fov_full, dim3(r.n_items), dim3(64), 0, stream, r);
+		else hipLaunchKernelGGL(k_render_bwd_fov, dim3(r.n_items), dim3(64), 0, stream, r);
+		const int rc0 = check_launch(full ? "render_bwd_fov_full" : "render_bwd_fov", stream, a.debug);
 		if (rc0) return rc0;
 	}
 	mark(1);
-	BwdFovFullArgs p = {}; // (every field of BwdPreArgs the chain rule does not get below: null / 0 -- no raw parameters, dense rows, no ranges)
-	p.pre.P = (int)P; p.pre.D = a->sh_degree; p.pre.M = a->M; p.pre.W = st->W; p.pre.H = st->H;
-	p.pre.tanfovx = a->tanfovx; p.pre.tanfovy = a->tanfovy;
-	p.pre.focal_y = st->H / (2.0f * a->tanfovy); p.pre.focal_x = st->W / (2.0f * a->tanfovx);
-	p.pre.scale_modifier = a->scale_modifier;
-	p.pre.means3D = a->means3D; p.pre.scales = a->scales; p.pre.rotations = a->rotations; p.pre.shs_rest = a->M > 1 ? a->shs_rest : nullptr;
-	p.pre.viewmatrix = a->viewmatrix; p.pre.projmatrix = a->projmatrix; p.pre.campos = a->campos;
-	p.pre.rec = geom.rec;
-	p.pre.dL_dmean2D = a->dL_dmeans2D; p.pre.dL_dconic = a->dL_dconic; p.pre.dL_dmean3D = a->dL_dmeans3D;
-	p.pre.dL_dsh_rest = a->dL_dshs_rest; p.pre.dL_dscale = a->dL_dscales; p.pre.dL_drot = a->dL_drotations;
-	p.pre.vis_list = geom.vis_list; p.pre.vis_count = geom.slab_ctr + 1; p.pre.lrange = geom.lrange;
-	p.pre.M0 = 1; p.pre.range_k = -1;
-	p.acc = fg.acc; p.mom = fg.mom; p.lvl = geom.lvl;
-	p.dL_dopacities = a->dL_dopacities; p.dL_dshs_dcs = a->dL_dshs_dcs; p.dL_dlevel_colours = a->dL_dlevel_colours; p.L = L;
+	BwdFovAppArgs lv;
+	lv.acc = acc; lv.lvl = geom.lvl; lv.vis_list = geom.vis_list; lv.vis_count = geom.slab_ctr + 1; lv.lrange = geom.lrange;
+	lv.dL_dopacities = a.dL_dopacities; lv.dL_dshs_dcs = a.dL_dshs_dcs; lv.dL_dlevel_colours = a.dL_dlevel_colours; lv.L = L;
 	const int pblocks = (int)((P + 255) / 256);
-	hipLaunchKernelGGL(k_fov_full_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
-	const int rc2 = check_launch("fov_full_bwd", stream, a->debug);
+	if (full)
+	{
+		BwdFovFullArgs p = {}; // (every field of BwdPreArgs the chain rule does not get below: null / 0 -- no raw parameters, dense rows, no ranges)
+		p.lv = lv; p.mom = mom;
+		p.pre.P = (int)P; p.pre.D = full->sh_degree; p.pre.M = full->M; p.pre.W = st->W; p.pre.H = st->H;
+		p.pre.tanfovx = full->tanfovx; p.pre.tanfovy = full->tanfovy;
+		p.pre.focal_y = st->H / (2.0f * full->tanfovy); p.pre.focal_x = st->W / (2.0f * full->tanfovx);
+		p.pre.scale_modifier = full->scale_modifier;
+		p.pre.means3D = full->means3D; p.pre.scales = full->scales; p.pre.rotations = full->rotations; p.pre.shs_rest = full->M > 1 ? full->shs_rest : nullptr;
+		p.pre.viewmatrix = full->viewmatrix; p.pre.projmatrix = full->projmatrix; p.pre.campos = full->campos;
+		p.pre.rec = geom.rec;
+		p.pre.dL_dmean2D = full->dL_dmeans2D; p.pre.dL_dconic = full->dL_dconic; p.pre.dL_dmean3D = full->dL_dmeans3D;
+		p.pre.dL_dsh_rest = full->dL_dshs_rest; p.pre.dL_dscale = full->dL_dscales; p.pre.dL_drot = full->dL_drotations;
+		p.pre.M0 = 1; p.pre.range_k = -1;
+		hipLaunchKernelGGL(k_fov_full_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, p);
+	}
+	else hipLaunchKernelGGL(k_fov_appearance_bwd, dim3(pblocks < 2048 ? pblocks : 2048), dim3(256), 0, stream, lv);
+	const int rc2 = check_launch(full ? "fov_full_bwd" : "fov_appearance_bwd", stream, a.debug);
 	mark(2);
 	return rc2;
+}
+
+int launch_backward_fov_appearance(const fr_backward_fov_args *a) { return launch_backward_fov({ *a, nullptr }); }
+int launch_backward_fov_full(const fr_backward_fov_full_args *a)
+{
+	return launch_backward_fov({ { a->size, a->debug, a->state, a->background, a->dL_dpix, a->dL_dopacities, a->dL_dshs_dcs, a->dL_dlevel_colours,
+		a->stream, a->stage_events, a->blend_pairs }, a });
 }
 
 } // namespace fr

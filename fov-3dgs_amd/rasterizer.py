@@ -746,6 +746,17 @@ def _forward_native(*args, **kw):
 POISON_GRADIENTS = False
 
 
+def _gradient_allocator(dev, P):
+    """z(*shape) for the gradient tensors of a backward call over P rows. The library writes every element (zero rows included), so
+    nothing is zero-filled here (the reference zero-fills 1.8 GB per step at 6 M Gaussians); P == 0 never reaches the library, hence
+    zeros for that case; NaN under POISON_GRADIENTS."""
+    if P == 0:
+        return lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+    if POISON_GRADIENTS:
+        return lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    return lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+
+
 def _alloc_gradients(z, P, M0, Mrest, has_cov, has_col):
     """The dense gradient tensors of one backward call, in _backward_native's order; z(*shape) allocates."""
     return (z(P, 3), z(P, 3), z(P, 1), z(P, 6) if has_cov else None, z(P, 3) if has_col else None, z(P, M0, 3), z(P, 3), z(P, 4),
@@ -777,10 +788,7 @@ def prefill_gradients(dev, P, M0, Mrest, has_cov, has_col, has_sh, radii=None):
     with torch.cuda.device(dev):
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev)
-        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        if POISON_GRADIENTS:
-            z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-        g = _alloc_gradients(z, P, M0, Mrest, has_cov, has_col)
+        g = _alloc_gradients(_gradient_allocator(dev, P), P, M0, Mrest, has_cov, has_col)
         a = _native.BackwardArgs()
         a.P, a.M = P, M0 + (Mrest or 0)
         a.radii = radii.data_ptr() if radii is not None else None
@@ -853,12 +861,7 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
         rest_c = put("shs_rest", sh_rest)
         M0 = 0 if sh_c is None else sh_c.size(1)
         M = M0 + (0 if rest_c is None else rest_c.size(1))
-        # every gradient tensor is written in full by fr_backward (zero rows included): no zero fill here (the reference
-        # zero-fills 1.8 GB per step at 6 M Gaussians); P == 0 never reaches the library, hence zeros for that case
-        z = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)) if P != 0 else \
-            (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
-        if POISON_GRADIENTS and P != 0:
-            z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+        z = _gradient_allocator(dev, P)
         # outputs only when the 3D covariances / colours are inputs; otherwise intermediates the library keeps per
         # visible Gaussian in its geometry workspace
         has_cov = want_cov3D_grad or (cov3Ds_precomp is not None and cov3Ds_precomp.numel() != 0)
@@ -936,6 +939,23 @@ def _backward_native(variant, rs, means3D, radii, colors_precomp, opacities, sca
     return out + (dL_dsh_rest,) if dL_dsh_rest is not None else out
 
 
+def _call_fov_backward(fn, a, state, bg, grad_out_color, dev, stage_events, blend_pairs, debug):
+    """What fr_backward_fov_appearance and fr_backward_fov share: the fields their argument structs have in common (`a`: either struct,
+    the caller has filled in the rest), the call on the current stream and the error."""
+    a.size, a.debug = C.sizeof(a), int(bool(debug))
+    a.state = C.pointer(state)
+    a.stream = torch.cuda.current_stream(dev).cuda_stream
+    bg_c, dpix = _f32_small(bg, dev, a.stream), _f32(grad_out_color, dev)
+    a.background, a.dL_dpix = _ptr(bg_c), _ptr(dpix)
+    if stage_events is not None:
+        a.stage_events = stage_events
+    if blend_pairs is not None:
+        a.blend_pairs = blend_pairs.data_ptr()
+    rc = fn(C.byref(a))
+    if rc != 0:
+        raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
+
+
 def _backward_fov_native(state, bg, grad_out_color, want_colours=False, stage_events=None, blend_pairs=None, debug=False):
     """fr_backward_fov_appearance over a kept forward state (a _native.FovState filled by the state-keeping forward, whose workspaces the
     caller still holds) -> (dL_dopacities [P,L], dL_dshs_dcs [P,L,3], dL_dlevel_colours [P,L,3] or None), on the current stream.
@@ -943,28 +963,14 @@ def _backward_fov_native(state, bg, grad_out_color, want_colours=False, stage_ev
     lib = _native.load()
     dev = grad_out_color.device
     P, L = int(state.P), int(state.levels)
-    z = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)) if P != 0 else \
-        (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
-    if POISON_GRADIENTS and P != 0:
-        z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    z = _gradient_allocator(dev, P)
     with torch.cuda.device(dev):
         g_op, g_dc = z(P, L), z(P, L, 3)
         g_col = z(P, L, 3) if want_colours else None
         if P != 0:
             a = _native.BackwardFovArgs()
-            a.size, a.debug = C.sizeof(_native.BackwardFovArgs), int(bool(debug))
-            a.state = C.pointer(state)
-            bg_c, dpix = _f32_small(bg, dev), _f32(grad_out_color, dev)
-            a.background, a.dL_dpix = bg_c.data_ptr(), dpix.data_ptr()
             a.dL_dopacities, a.dL_dshs_dcs, a.dL_dlevel_colours = g_op.data_ptr(), g_dc.data_ptr(), _ptr(g_col)
-            a.stream = torch.cuda.current_stream(dev).cuda_stream
-            if stage_events is not None:
-                a.stage_events = stage_events
-            if blend_pairs is not None:
-                a.blend_pairs = blend_pairs.data_ptr()
-            rc = lib.fr_backward_fov_appearance(C.byref(a))
-            if rc != 0:
-                raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
+            _call_fov_backward(lib.fr_backward_fov_appearance, a, state, bg, grad_out_color, dev, stage_events, blend_pairs, debug)
     return g_op, g_dc, g_col
 
 
@@ -979,10 +985,7 @@ def _backward_fov_full_native(state, rs, means3D, scales, rotations, shs_rest, g
         raise RuntimeError("fovraster: the loaded library has no full foveated backward pass (fr_backward_fov): rebuild it")
     dev = grad_out_color.device
     P, L = int(state.P), int(state.levels)
-    z = (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)) if P != 0 else \
-        (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
-    if POISON_GRADIENTS and P != 0:
-        z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    z = _gradient_allocator(dev, P)
     with torch.cuda.device(dev):
         m, sc, ro, rest = (_f32(t.detach(), dev) for t in (means3D, scales, rotations, shs_rest))
         nrest = 0 if rest is None else int(rest.size(1))
@@ -991,26 +994,15 @@ def _backward_fov_full_native(state, rs, means3D, scales, rotations, shs_rest, g
                    dL_dconic=z(P, 4) if want_conic else None)
         if P != 0:
             a = _native.BackwardFovFullArgs()
-            a.size, a.debug = C.sizeof(_native.BackwardFovFullArgs), int(bool(debug))
-            a.state = C.pointer(state)
             a.P, a.M, a.sh_degree = P, 1 + nrest, int(rs.sh_degree)
             a.tanfovx, a.tanfovy, a.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
             sh_ = torch.cuda.current_stream(dev).cuda_stream
-            small = [_f32_small(t, dev, sh_) for t in (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg)]
-            dpix = _f32(grad_out_color, dev)
+            small = [_f32_small(t, dev, sh_) for t in (rs.viewmatrix, rs.projmatrix, rs.campos)]
             a.means3D, a.scales, a.rotations, a.shs_rest = _ptr(m), _ptr(sc), _ptr(ro), _ptr(rest)
-            a.viewmatrix, a.projmatrix, a.campos, a.background = (_ptr(t) for t in small)
-            a.dL_dpix = dpix.data_ptr()
+            a.viewmatrix, a.projmatrix, a.campos = (_ptr(t) for t in small)
             for k, t in out.items():
                 setattr(a, k, _ptr(t) if t is not None and t.numel() else None)
-            a.stream = sh_
-            if stage_events is not None:
-                a.stage_events = stage_events
-            if blend_pairs is not None:
-                a.blend_pairs = blend_pairs.data_ptr()
-            rc = lib.fr_backward_fov(C.byref(a))
-            if rc != 0:
-                raise RuntimeError(f"fovraster backward failed ({rc}): {_native.last_error()}")
+            _call_fov_backward(lib.fr_backward_fov, a, state, rs.bg, grad_out_color, dev, stage_events, blend_pairs, debug)
     return out
 
 

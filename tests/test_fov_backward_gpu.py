@@ -275,6 +275,38 @@ def test_a_second_backward_over_the_same_state_gives_the_same_gradients():
     compare(second, ref.backward(dL), 4, "second call", MAIN_ROWS)
 
 
+def test_outputs_that_are_not_16_byte_aligned_are_written_in_full_and_nothing_beside_them():
+    """The fill's fallback for a tensor its 16-byte stores cannot take (hipMemsetAsync): every output is the [1:-1] view of a NaN-filled
+    buffer two floats longer, so each pointer is 4 bytes off alignment. The call succeeds, every element of the views is written, the
+    guard element on either side of each is untouched, and the gradients are those of the aligned call over the same state."""
+    _need_gpu()
+    scene, cam, ofwd, ref, dL = R.case(**R.MAIN)
+    fwd = keep_forward(scene, cam)
+    first = backward(fwd, dL)
+    st, rs = fwd["state"], fwd["rs"]
+    P, L = int(st.P), int(st.levels)
+    bufs = {k: torch.full((n + 2,), float("nan"), dtype=torch.float32, device=DEV)
+            for k, n in (("dL_dopacities", P * L), ("dL_dshs_dcs", 3 * P * L), ("dL_dlevel_colours", 3 * P * L))}
+    views = {k: b[1:-1] for k, b in bufs.items()}
+    a = _native.BackwardFovArgs()
+    a.size, a.debug, a.state = C.sizeof(_native.BackwardFovArgs), 1, C.pointer(st)
+    bg, dpix = rs.bg.to(DEV).float().contiguous(), _t(dL, DEV).float().contiguous()
+    a.background, a.dL_dpix = bg.data_ptr(), dpix.data_ptr()
+    for k, v in views.items():
+        assert v.data_ptr() % 16 == 4, k
+        setattr(a, k, v.data_ptr())
+    a.stream = torch.cuda.current_stream(DEV).cuda_stream
+    rc = _native.load().fr_backward_fov_appearance(C.byref(a))
+    torch.cuda.synchronize()
+    assert rc == 0, _native.last_error()
+    for k, b in bufs.items():
+        assert bool(torch.isfinite(views[k]).all()), k
+        assert bool(torch.isnan(b[0])) and bool(torch.isnan(b[-1])), f"{k}: a guard element was written"
+    second = {k: v.cpu().numpy().reshape(first[k].shape) for k, v in views.items()}
+    for k in first:
+        check_grad(R.rows(second[k], 4), R.rows(first[k], 4), f"unaligned {k}", min_rows=MAIN_ROWS)
+
+
 def test_fine_tuning_the_opacities_through_the_foveated_renderer():
     """The use the pass is for: Adam on the per-level opacities against an image rendered from other opacities, L1 loss, twenty steps:
     the loss falls below half its start; and one step against the foveated metameric loss (HVSLoss's defaults) at the frame's gaze

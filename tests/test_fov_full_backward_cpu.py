@@ -119,6 +119,49 @@ def test_refusals_name_the_field_before_anything_is_enqueued():
     assert lib.fr_backward_fov_appearance(C.byref(b)) != 0 and "variant" in _native.last_error()
 
 
+def _set(**fields):
+    def change(st):
+        for k, v in fields.items():
+            setattr(st, k, v)
+    return change
+
+
+# every malformed state either entry point refuses -> the field its message names
+MALFORMED = (("short size", _set(size=8), "fr_fov_state.size"), ("wrong variant", None, "variant"), ("levels 1", _set(levels=1), "levels"),
+             ("levels 5", _set(levels=5), "levels"), ("W = 0", _set(W=0), "W=0"), ("W < 0", _set(W=-16), "W=-16"), ("H = 0", _set(H=0), "H=0"),
+             ("H < 0", _set(H=-16), "H=-16"), ("num_rendered < 0", _set(num_rendered=-1), "num_rendered=-1"),
+             ("num_items > 4 T", _set(num_items=4 * 4 + 1), "num_items=17"), ("null geometry", _set(geometry=None), "geometry"),
+             ("null image", _set(image=None), "image"), ("null binning", _set(binning=None), "binning"))
+
+
+def test_both_backward_entry_points_refuse_the_same_malformed_states():
+    """fr_backward_fov_appearance and fr_backward_fov check the state they are handed with one validator: a state one of them refuses
+    for its sizes, variant, levels or workspaces is refused by the other, FR_ERR_INVALID, with the same field named."""
+    lib = _native.load()
+
+    def appearance(st):
+        b = _native.BackwardFovArgs()
+        b.size, b.state = C.sizeof(_native.BackwardFovArgs), None if st is None else C.pointer(st)
+        b.background = b.dL_dpix = b.dL_dopacities = b.dL_dshs_dcs = 4096
+        return lib.fr_backward_fov_appearance(C.byref(b))
+
+    def full(st):
+        a = _args(st if st is not None else _state())
+        if st is None:
+            a.state = None
+        return lib.fr_backward_fov(C.byref(a))
+    for entry, own in ((appearance, 3), (full, 3 | _native.FOV_STATE_FULL)):
+        assert entry(None) == -1 and "state" in _native.last_error(), entry.__name__
+        for what, change, field in MALFORMED:
+            st = _state(variant=own)
+            if change is None:
+                st.variant = 1 | (own & _native.FOV_STATE_FULL)
+            else:
+                change(st)
+            assert entry(st) == -1, (entry.__name__, what)   # FR_ERR_INVALID
+            assert field in _native.last_error(), (entry.__name__, what, _native.last_error())
+
+
 def test_the_full_forward_refuses_what_the_keep_forward_refuses():
     from tests.test_fov_backward_cpu import _forward_args
     lib = _native.load()
