@@ -57,6 +57,11 @@ class ForwardExt(C.Structure):
     _fields_ = [("size", C.c_uint32), ("visibility", _FP)]
 
 
+class ForwardAux(C.Structure):
+    """fr_forward_aux: the per-pixel depth / coverage planes of fr_forward_begin_aux / fr_forward_aux_call (both [H*W] float32)"""
+    _fields_ = [("size", C.c_uint32), ("depth", _FP), ("coverage", _FP)]
+
+
 class Foveation(C.Structure):
     """fr_foveation: the layer count and display geometry of one foveated call (fr_forward_begin_fov / fr_forward_fov_call)"""
     _fields_ = [("size", C.c_uint32), ("levels", C.c_int32), ("max_pooling_size", C.c_float), ("real_image_width", C.c_float),
@@ -191,7 +196,8 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_vq_workspace_bytes", "fr_vq_nearest", "fr_vq_gather", "fr_vq_update", "fr_vq_replace", "fr_pack_bits", "fr_unpack_bits",
            "fr_forward_begin_fov_keep", "fr_forward_fov_keep_call", "fr_geometry_bytes_fov_keep", "fr_image_bytes_fov_keep",
            "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance",
-           "fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov")
+           "fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov",
+           "fr_forward_begin_aux", "fr_forward_aux_call")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -202,7 +208,9 @@ FOV_BACKWARD_EXPORTS = ("fr_forward_begin_fov_keep", "fr_forward_fov_keep_call",
                         "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance")
 # ... and its full backward pass (geometry, rest SH): has_fov_full_backward(); without it differentiable=True on that renderer raises
 FOV_FULL_BACKWARD_EXPORTS = ("fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov")
-OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS + FOV_BACKWARD_EXPORTS + FOV_FULL_BACKWARD_EXPORTS
+# ... and the inference renderers' depth / coverage outputs (fr_forward_aux): has_forward_aux(); without them want_depth=True raises
+FORWARD_AUX_EXPORTS = ("fr_forward_begin_aux", "fr_forward_aux_call")
+OPTIONAL_EXPORTS = EXT_EXPORTS + FOVEATION_EXPORTS + FOV_BACKWARD_EXPORTS + FOV_FULL_BACKWARD_EXPORTS + FORWARD_AUX_EXPORTS
 FOV_STATE_FULL = 0x100  # FR_FOV_STATE_FULL: set in fr_fov_state.variant by the _full forward
 
 _lib = None
@@ -322,6 +330,12 @@ def load():
         lib.fr_geometry_level_colours_hi.restype = C.c_void_p
         lib.fr_pack_colour_fov.argtypes = [C.c_int32, _FP, _FP, C.c_int32, _FP, C.c_void_p]
         lib.fr_pack_colour_fov.restype = C.c_int
+    if has_forward_aux(lib):
+        lib.fr_forward_begin_aux.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(ForwardAux),
+                                             C.POINTER(C.c_void_p)]
+        lib.fr_forward_begin_aux.restype = C.c_int
+        lib.fr_forward_aux_call.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(ForwardAux)]
+        lib.fr_forward_aux_call.restype = C.c_int
     if has_fov_backward(lib):
         lib.fr_forward_begin_fov_keep.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(Foveation), C.POINTER(FovState),
                                                   C.POINTER(C.c_void_p)]
@@ -429,6 +443,12 @@ def has_foveation(lib=None):
     """the loaded library takes fr_foveation settings (else: only the reference's constants, and anything else is refused)"""
     lib = load() if lib is None else lib
     return all(hasattr(lib, n) for n in FOVEATION_EXPORTS)
+
+
+def has_forward_aux(lib=None):
+    """the loaded library writes the inference renderers' depth / coverage planes (fr_forward_aux)"""
+    lib = load() if lib is None else lib
+    return all(hasattr(lib, n) for n in FORWARD_AUX_EXPORTS)
 
 
 def has_fov_backward(lib=None):

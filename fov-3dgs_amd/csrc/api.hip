@@ -304,12 +304,31 @@ static int validate_fov_state(const fr_fov_state *st, const char *who, bool full
 	return FR_OK;
 }
 
+// what a call with fr_forward_aux refuses, before anything is enqueued (the message names the cause); a struct with neither pointer
+// asks for nothing
+static int validate_aux(const fr_forward_args *a, const fr_forward_aux *aux, int keep)
+{
+	if (!aux) return FR_OK;
+	if (aux->size < sizeof(fr_forward_aux)) { set_error("fr_forward_aux.size is %u, expected at least %u", aux->size, (unsigned)sizeof(fr_forward_aux)); return FR_ERR_INVALID; }
+	if ((aux->depth != nullptr) != (aux->coverage != nullptr))
+	{ set_error("fr_forward_aux: depth and coverage go together (both planes or neither); only %s is set", aux->depth ? "depth" : "coverage"); return FR_ERR_INVALID; }
+	if (!aux->depth) return FR_OK;
+	if (a->variant != FR_VARIANT_FOV_PCHECK_OBB && a->variant != FR_VARIANT_PCHECK_OBB)
+	{ set_error("fr_forward_aux: depth / coverage are outputs of variant %d (fov_pcheck_obb) and variant %d (pcheck_obb) only, not of variant %d",
+		FR_VARIANT_FOV_PCHECK_OBB, FR_VARIANT_PCHECK_OBB, a->variant); return FR_ERR_INVALID; }
+	if (keep) { set_error("fr_forward_aux: depth / coverage are outputs of the inference frame, not of the state-keeping forwards (_keep, _keep_full)"); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
 // keep: 0 = the inference frame, 1 = the state-keeping forward, 2 = the same for the full backward pass (fr_forward_begin_fov_keep_full)
-static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, int keep, fr_frame **out)
+static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, fr_fov_state *keep_state, int keep, fr_frame **out,
+	const fr_forward_aux *aux = nullptr)
 {
 	if (!out) { set_error("null frame handle"); return FR_ERR_INVALID; }
 	*out = nullptr;
 	int rc = validate_forward(a);
+	if (rc) return rc;
+	rc = validate_aux(a, aux, keep);
 	if (rc) return rc;
 	if (keep) { rc = validate_fov_keep(a, fov, keep_state); if (rc) return rc; }
 	if (ext && ext->size < sizeof(fr_forward_ext)) { set_error("fr_forward_ext.size is %u, expected at least %u", ext->size, (unsigned)sizeof(fr_forward_ext)); return FR_ERR_INVALID; }
@@ -328,6 +347,7 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	c.visibility = ext ? ext->visibility : nullptr; // (read here: ext need not outlive this call)
 	c.fov = fov_params(fov);                        // (likewise: the settings travel in the kernels' arguments)
 	c.keep = keep ? 1 : 0;
+	if (aux) { c.aux_depth = aux->depth; c.aux_cov = aux->coverage; } // (likewise read here)
 	f->keep_state = keep ? keep_state : nullptr;
 	if (keep)
 	{
@@ -340,6 +360,11 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	{
 		// reference: RasterizeGaussiansCUDA returns the zero-initialised image when P == 0
 		FR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)a->W * a->H, stream));
+		if (c.aux_depth)
+		{
+			FR_HIP(hipMemsetAsync(c.aux_depth, 0, sizeof(float) * (size_t)a->W * a->H, stream));
+			FR_HIP(hipMemsetAsync(c.aux_cov, 0, sizeof(float) * (size_t)a->W * a->H, stream));
+		}
 		f->empty = true;
 		*out = f; guard.f = nullptr;
 		return FR_OK;
@@ -406,6 +431,9 @@ static int forward_begin(fr_forward_args *a, const fr_forward_ext *ext, const fr
 	c.totals_seq = seq;
 	mark(FR_STAGE_TILE_LEVELS);
 	if (is_fov(a->variant)) { rc = launch_tile_levels(c); if (rc) return rc; }
+	// fr_forward_aux: the two level states of a two-level tile ADD their halves to the depth / coverage planes as they do to the image;
+	// those tiles of the two planes are cleared by a kernel of their own, launched in such calls only (k_project's code stays what it is)
+	if (c.fov_split && c.aux_depth) { rc = launch_aux_clear(c); if (rc) return rc; }
 	if (c.geom.pad_op) { rc = launch_pad_levels(c); if (rc) return rc; } // (fr_foveation.levels other than 4 and 8)
 	mark(FR_STAGE_PROJECT);
 	rc = launch_project(c); if (rc) return rc;
@@ -547,6 +575,19 @@ int fr_forward_fov_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_
 {
 	fr_frame *f = nullptr;
 	const int rc = fr_forward_begin_fov(a, ext, fov, &f);
+	if (rc) return rc;
+	return fr_forward_finish(f);
+}
+
+int fr_forward_begin_aux(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, const fr_forward_aux *aux, fr_frame **out)
+{
+	return forward_begin(a, ext, fov, nullptr, 0, out, aux);
+}
+
+int fr_forward_aux_call(fr_forward_args *a, const fr_forward_ext *ext, const fr_foveation *fov, const fr_forward_aux *aux)
+{
+	fr_frame *f = nullptr;
+	const int rc = fr_forward_begin_aux(a, ext, fov, aux, &f);
 	if (rc) return rc;
 	return fr_forward_finish(f);
 }

@@ -540,6 +540,8 @@ struct FwdCtx {
 	uint32_t *keep_n = nullptr;
 	float4 *keep_acc = nullptr; // ... and the items' rows of gradient sums (FovKeepGeom::acc) are cleared
 	float4 *keep_mom = nullptr; // fr_forward_begin_fov_keep_full: the items' rows of geometry moments (FovFullGeom::mom), cleared as well
+	float *aux_depth = nullptr; // fr_forward_aux of the call (both or neither): the blend's depth instantiation writes the two planes
+	float *aux_cov = nullptr;
 	GeomWS geom;
 	ImageWS img;
 	BinWS bin;
@@ -586,6 +588,7 @@ int launch_backward(const fr_backward_args *a);
 int launch_backward_appearance(const fr_backward_args *a);
 // fr_backward_fov_appearance: the foveated lean tile pass over the forward's work items and k_fov_appearance_bwd
 int launch_backward_fov_appearance(const fr_backward_fov_args *a);
+int launch_aux_clear(FwdCtx &c); // fr_forward_aux, RF: the two-level tiles of the depth / coverage planes start as zeros (render.hip)
 int launch_fov_keep_clear(FwdCtx &c); // the state-keeping forward: the rows of sums of the frame's items start as zeros
 // fr_backward_fov: the foveated nine-sum tile pass over the forward's work items and k_fov_full_bwd (the whole chain rule)
 int launch_backward_fov_full(const fr_backward_fov_full_args *a);

@@ -18,6 +18,7 @@
 // launches two full grids that early-return on each other's tiles).
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef FR_RENDER_GROUP
 #define FR_RENDER_GROUP 2       // RF: entries whose transmittance-independent part is evaluated together
@@ -76,6 +77,10 @@ __device__ __forceinline__ v2f exp_neg_pair(v2f q)
 	const v2f t = q * -1.4426950408889634f;
 	return (v2f){ __builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y) };
 }
+
+// DEPTH instantiations (fr_forward_aux): the sums of w z of a lane's pixels, one packed pair per half; an empty struct elsewhere
+template <int HP> struct DepthAcc { v2f v[HP]; float pz; }; // pz: the prefetched entry's view-space depth
+struct NoDepthAcc {};
 
 // Two pixels (rows) of a lane: transmittance (negated once the pixel is finished) and colour sums.
 struct Px2 { v2f T, C0, C1, C2; };
@@ -159,8 +164,10 @@ struct RenderArgs {
 	int T;
 	const float *bg;
 	float *out_color;
-	float *final_T;
-	uint32_t *n_contrib;
+	// (the DEPTH instantiations, fr_forward_aux, are inference frames, which keep neither state array: the two planes [W*H] they write
+	// travel in the same slots, so the struct -- the kernel argument of every instantiation -- is what it was)
+	union { float *final_T; float *depth; };
+	union { uint32_t *n_contrib; float *coverage; };
 	int *gaussians_count;   // RS / MAX / LWMC
 	float *contributions;   // RS / MAX / LWMC
 	const float *loss_map;  // LWMC
@@ -193,9 +200,13 @@ __device__ __forceinline__ void report_consumed(const RenderArgs &a, int tile, i
 // done at a round boundary sets the round's bit in round_flags (one atomicOr per wave and round); whoever finds the bit
 // clear owns the round and adds the counts of its (up to) 256 entries as it walks them -- to the end of the round even
 // if its own band finishes in between. A round nobody claims was not started.
-template <int VARIANT, int PPL>
+// DEPTH (fr_forward_aux, PCHECK_OBB only): the same blend -- the image is the plain instantiation's bit for bit -- that also sums
+// w z over the pairs it accumulates (z: the view-space depth the sort key was made of, the record's r[2].y) and writes it with the
+// coverage 1 - T_end; the plain instantiations' code is what it was.
+template <int VARIANT, int PPL, bool DEPTH = false>
 __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 {
+	static_assert(!DEPTH || VARIANT == FR_VARIANT_PCHECK_OBB, "depth / coverage: the inference variant only");
 	// (FR_VARIANT_SUM_NOSTATS, internal: pcheck_obb_sum for a caller that drops the statistics, fr_forward_args.no_stats)
 	// (FR_VARIANT_COUNT, internal: ORIGINAL's arithmetic -- same image, final_T, n_contrib bit for bit -- plus gaussians_count[i] = the
 	// (pixel, Gaussian i) pairs that were accumulated: LightGaussian's renderCUDA_count, compress-diff-gaussian-rasterization
@@ -221,6 +232,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 	__shared__ float2 s2[64];   // b, tq: the threshold on q = -power below which a pixel takes part (see the staging)
 	__shared__ int sid[NEEDID ? 64 : 1];
 	__shared__ int stqa[PMAX ? 64 : 1]; // _max: the alpha test's threshold on q beside the support's (see the staging)
+	__shared__ float sz[DEPTH ? 64 : 1]; // DEPTH: the entries' view-space depths
 
 	const int st = threadIdx.x; // lane = staging slot
 	if (blockIdx.x >= a.totals[5] || a.totals[0] > a.capacity || a.totals[5] > gridDim.x) return;
@@ -251,6 +263,13 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 	}
 #pragma unroll
 	for (int h = 0; h < HP; h++) S[h].C0 = S[h].C1 = S[h].C2 = (v2f){ 0.f, 0.f };
+	std::conditional_t<DEPTH, DepthAcc<HP>, NoDepthAcc> dz; // DEPTH: sum of w z per pixel
+	if constexpr (DEPTH)
+	{
+#pragma unroll
+		for (int h = 0; h < HP; h++) dz.v[h] = (v2f){ 0.f, 0.f };
+		dz.pz = 0.0f;
+	}
 	float best_w[LWMC ? PPL : 1];   // LWMC forward.cu:347-348: running max contribution per pixel ...
 	int best_id[LWMC ? PPL : 1];    // ... and whose it is (defaults to Gaussian 0, as in the reference)
 #pragma unroll
@@ -265,6 +284,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 		pid = a.point_list[range.x + st];
 		const float4 *r = a.rec + 3 * (size_t)pid;
 		p0 = r[0]; p1 = r[1];
+		if constexpr (DEPTH) dz.pz = r[2].y;
 		// (statistics: the Gaussian's index is the last word of the item's own record -- the same cache line as the colour's third
 		// channel -- where round 4 gathered it from vis_list, a line of its own per entry)
 		if (NEEDID) { const float4 r2 = r[2]; p2 = r2.x; pgid = __float_as_uint(r2.w); } else p2 = r[2].x;
@@ -322,6 +342,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 			s0[st] = p0; s1[st] = p1; s2[st] = make_float2(p2, tq);
 			if (NEEDID) sid[st] = (int)pgid;
 			if (PMAX) stqa[st] = __float_as_int(lq >= 0.0f ? fminf(4.5f, lq) : -1.0f);
+			if constexpr (DEPTH) sz[st] = dz.pz;
 		}
 		unsigned long long reach_own;
 		{
@@ -338,6 +359,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 			pid = a.point_list[range.x + base + 64 + st];
 			const float4 *r = a.rec + 3 * (size_t)pid;
 			p0 = r[0]; p1 = r[1];
+			if constexpr (DEPTH) dz.pz = r[2].y;
 			if (NEEDID) { const float4 r2 = r[2]; p2 = r2.x; pgid = __float_as_uint(r2.w); } else p2 = r[2].x;
 		}
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // lanes read entries other lanes staged
@@ -397,6 +419,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 				v2f w; bool ax, ay;
 				blend2k<true>(S[h], t.okx[h], t.oky[h], t.e[h], t.col, w, ax, ay);
 				if (COUNT) hits += __popcll(__ballot(ax)) + __popcll(__ballot(ay));
+				if constexpr (DEPTH) { const float z = sz[j]; dz.v[h] = __builtin_elementwise_fma((v2f){ z, z }, w, dz.v[h]); } // (w is an exact zero for a pair that is not accumulated)
 				if (AUX)
 				{
 					last[2 * h] = ax ? (uint32_t)(base + j + 1) : last[2 * h];
@@ -503,6 +526,7 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 		a.out_color[pid2] = fmaf(Tk, bg0, S[k >> 1].C0[k & 1]);
 		a.out_color[plane + pid2] = fmaf(Tk, bg1, S[k >> 1].C1[k & 1]);
 		a.out_color[2 * plane + pid2] = fmaf(Tk, bg2, S[k >> 1].C2[k & 1]);
+		if constexpr (DEPTH) { a.depth[pid2] = dz.v[k >> 1][k & 1]; a.coverage[pid2] = 1.0f - Tk; }
 	}
 }
 
@@ -528,10 +552,18 @@ __global__ void __launch_bounds__(64) k_render(const RenderArgs a)
 // RenderArgs::final_T / n_contrib ([2][W*H] each here). A state-1 pixel that starts finished (est > L2) keeps T = 1, n = 0. The
 // instantiation has launch bounds of its own (two more registers for the positions: it need not hold eight waves); the inference
 // instantiation's code is what it was.
-template <int PPL, bool KEEP = false>
-__global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArgs a)
+//
+// DEPTH (fr_forward_aux): the same blend again -- the image is the inference image bit for bit -- that also sums w z over the pairs it
+// accumulates, w = alpha T as blend2k hands it out and z the entry's view-space depth (the record's r[2].y, staged in a free slot of
+// s1: no more LDS), one more packed pair per half, and writes it with the coverage 1 - T_end to RenderArgs::depth / coverage: stored
+// outright in a single-level tile, the two states' rounded shares added (atomicAdd, as the image's) in a two-level tile, whose pixels
+// k_aux_clear has cleared. Launch bounds as KEEP's: held to eight waves the allocator spills four registers; left the room of six
+// it settles on 64 registers without a spill, i.e. the instantiation still runs eight waves per SIMD.
+template <int PPL, bool KEEP = false, bool DEPTH = false>
+__global__ void __launch_bounds__(64, (KEEP || DEPTH) ? 6 : 8) k_render_fov(const RenderArgs a)
 {
 	static_assert(PPL == 2, "work items encode two bands per tile");
+	static_assert(!(KEEP && DEPTH), "depth / coverage are outputs of the inference frame");
 	constexpr int HP = PPL / 2;
 	// three rows of 16 bytes per staged entry, all with the same stride: one address register serves the three reads
 	__shared__ float4 s0[64];   // x, y, A, B
@@ -582,6 +614,13 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 		}
 #pragma unroll
 		for (int h = 0; h < HP; h++) S1[h].C0 = S1[h].C1 = S1[h].C2 = (v2f){ 0.f, 0.f };
+		std::conditional_t<DEPTH, DepthAcc<HP>, NoDepthAcc> dz; // DEPTH: sum of w z per pixel
+		if constexpr (DEPTH)
+		{
+#pragma unroll
+			for (int h = 0; h < HP; h++) dz.v[h] = (v2f){ 0.f, 0.f };
+			dz.pz = 0.0f;
+		}
 		uint32_t last[KEEP ? PPL : 1]; // KEEP: 1-based list position of the pixel's last contributor (n_contrib)
 #pragma unroll
 		for (int k = 0; k < (KEEP ? PPL : 1); k++) last[k] = 0;
@@ -592,7 +631,7 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 		// prefetch registers
 		float4 p0 = make_float4(0, 0, 0, 0), pl1 = p0;
 		float2 p1 = make_float2(0, 0);
-		// this wave's level row of every item (wave-uniform: a scalar base address)
+			// this wave's level row of every item (wave-uniform: a scalar base address)
 		// (a tile_min <= -1 -- a frame of a tile or two, whose tile centres lie outside it -- gives L1 = -1, where the reference
 		// indexes the previous Gaussian's level 3; such a tile never blends, and k_bin evaluated its level-0 rows: level 0)
 		const int lev = max(upper ? L2 : L1, 0);
@@ -604,6 +643,7 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 			p0 = r[0];
 			const float4 r1 = r[1];
 			p1 = make_float2(r1.x, r1.y);
+			if constexpr (DEPTH) dz.pz = r[2].y;
 			pl1 = lvrow[(size_t)id * FR_FOV_LEVELS];
 		};
 		if (lane < n) fetch(lane);
@@ -633,7 +673,13 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 			// only inside that expression's rounding, like the exp2-based test it replaces.
 			const float lq = logf(255.0f * pl1.w);
 			const float tq = lq >= 0.0f ? fminf(4.5f, lq) : 0.0f; // (false for the NaN of a negative opacity: takes part nowhere)
-			if (staged) { s0[lane] = p0; s1[lane] = make_float4(p1.x, tq, 0.0f, 0.0f); sl1[lane] = pl1; }
+			if (staged)
+			{
+				s0[lane] = p0;
+				if constexpr (DEPTH) s1[lane] = make_float4(p1.x, tq, dz.pz, 0.0f); // (the depth in a slot nobody else reads)
+				else s1[lane] = make_float4(p1.x, tq, 0.0f, 0.0f);
+				sl1[lane] = pl1;
+			}
 			unsigned long long reach_mask;
 			{
 				// alpha < 1/255 everywhere (forward.cu:563) <=> power < -ln(255 opacity): tighter than -4.5 for faint splats
@@ -712,6 +758,13 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 							last[2 * h] = ax ? (uint32_t)(base + jj[g] + 1) : last[2 * h];
 							last[2 * h + 1] = ay ? (uint32_t)(base + jj[g] + 1) : last[2 * h + 1];
 						}
+						else if constexpr (DEPTH)
+						{
+							v2f w; bool ax, ay;
+							const float z = s1[jj[g]].z; // (independent of the transmittance chain: the read is hoisted beside prepare()'s)
+							blend2k<true>(S1[h], t[g].inx[h], t[g].iny[h], t[g].e[h], t[g].c1, w, ax, ay);
+							dz.v[h] = __builtin_elementwise_fma((v2f){ z, z }, w, dz.v[h]); // (w is an exact zero for a pair that is not accumulated)
+						}
 						else blend2k<true>(S1[h], t[g].inx[h], t[g].iny[h], t[g].e[h], t[g].c1);
 					}
 			}
@@ -755,11 +808,18 @@ __global__ void __launch_bounds__(64, KEEP ? 6 : 8) k_render_fov(const RenderArg
 				atomicAdd(&a.out_color[pid], o0 * w);
 				atomicAdd(&a.out_color[plane + pid], o1 * w);
 				atomicAdd(&a.out_color[2 * plane + pid], o2 * w);
+				if constexpr (DEPTH)
+				{
+					// the state's share of both outputs; a state-1 pixel that started finished holds D = 0 and T = 1: it adds zeros
+					atomicAdd(&a.depth[pid], dz.v[k >> 1][k & 1] * w);
+					atomicAdd(&a.coverage[pid], (1.0f - t1) * w);
+				}
 				continue;
 			}
 			a.out_color[pid] = o0;
 			a.out_color[plane + pid] = o1;
 			a.out_color[2 * plane + pid] = o2;
+			if constexpr (DEPTH) { a.depth[pid] = dz.v[k >> 1][k & 1]; a.coverage[pid] = 1.0f - t1; }
 		}
 	}
 }
@@ -1034,6 +1094,36 @@ __global__ void __launch_bounds__(256) k_count_score(int P, const int32_t *__res
 	score[i] = (float)((double)hits[i] * (double)op);
 }
 
+// fr_forward_aux, RF: the two level states of a two-level tile ADD their shares to the depth and coverage planes (k_render_fov<.., DEPTH>),
+// so those tiles' pixels of the two planes start as zeros; every other tile is stored outright. One wave per tile, 16 rows of four
+// lanes, tile-wise as k_project clears the image: the kernel reads the flag row k_tile_levels wrote and touches the flagged tiles only.
+__global__ void __launch_bounds__(256) k_aux_clear(int T, int gx, int W, int H, const float *__restrict__ tile_bl, float *__restrict__ depth,
+	float *__restrict__ coverage)
+{
+	static_assert(FR_TILE == 16, "a wave clears a tile plane as 16 rows of four lanes");
+	const int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+	if (tile >= T || tile_bl[tile] == 0.0f) return;
+	const int x = (tile % gx) * FR_TILE + (lane & 3) * 4, y = (tile / gx) * FR_TILE + (lane >> 2);
+	if (y >= H) return;
+	const size_t at = (size_t)W * y + x;
+	const bool vec = (W & 3) == 0 && (((uintptr_t)depth | (uintptr_t)coverage) & 15) == 0; // (then every row piece is a whole, aligned float4)
+	if (vec)
+	{
+		if (x < W) { *(float4 *)(depth + at) = make_float4(0.f, 0.f, 0.f, 0.f); *(float4 *)(coverage + at) = make_float4(0.f, 0.f, 0.f, 0.f); }
+		return;
+	}
+#pragma unroll
+	for (int k = 0; k < 4; k++)
+		if (x + k < W) { depth[at + k] = 0.0f; coverage[at + k] = 0.0f; }
+}
+
+int launch_aux_clear(FwdCtx &c)
+{
+	hipLaunchKernelGGL(k_aux_clear, dim3((unsigned)((c.T + 3) / 4)), dim3(256), 0, c.stream, c.T, c.gx, c.a->W, c.a->H,
+		c.img.tile_lv + 4 * (size_t)c.T, c.aux_depth, c.aux_cov);
+	return check_launch("aux_clear", c.stream, c.a->debug);
+}
+
 int launch_render(FwdCtx &c)
 {
 	const fr_forward_args *a = c.a;
@@ -1049,6 +1139,7 @@ int launch_render(FwdCtx &c)
 	constexpr int PPL = 2;
 	r.round_flags = c.bin.round_flags;
 	r.consumed = a->list_consumed; r.pairs = a->blend_pairs;
+	if (c.aux_depth) { r.depth = c.aux_depth; r.coverage = c.aux_cov; } // (an inference frame: nobody reads final_T / n_contrib, see RenderArgs)
 	if (has_stats(a->variant) && !a->no_stats && a->variant != FR_VARIANT_PCHECK_OBB_MAX && c.bin.round_flags)
 	{
 		const hipError_t e = hipMemsetAsync(c.bin.round_flags, 0, round_flag_words(c.capacity, c.T) * sizeof(uint32_t), c.stream);
@@ -1068,13 +1159,17 @@ int launch_render(FwdCtx &c)
 	case FR_VARIANT_PCHECK_OBB_SUM:
 		if (a->no_stats) FR_LAUNCH_RENDER(FR_VARIANT_SUM_NOSTATS, false); else FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB_SUM, false);
 		break;
-	case FR_VARIANT_PCHECK_OBB: FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB, true); break;
+	case FR_VARIANT_PCHECK_OBB:
+		if (c.aux_depth) hipLaunchKernelGGL((k_render<FR_VARIANT_PCHECK_OBB, PPL, true>), dim3(n_items), dim3(64), 0, c.stream, r);
+		else FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB, true);
+		break;
 	case FR_VARIANT_PCHECK_OBB_MAX: FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB_MAX, true); break;
 	case FR_VARIANT_PCHECK_OBB_LWMC: FR_LAUNCH_RENDER(FR_VARIANT_PCHECK_OBB_LWMC, false); break;
 	case FR_VARIANT_NAIVE_FOV_PCHECK_OBB: hipLaunchKernelGGL((k_render_smfr<2>), dim3(n_items), dim3(64), 0, c.stream, r); break;
 	case FR_VARIANT_MMFR_PCHECK_OBB: hipLaunchKernelGGL((k_render_mmfr<2>), dim3(n_items), dim3(64), 0, c.stream, r); break;
 	default:
 		if (c.keep) hipLaunchKernelGGL((k_render_fov<2, true>), dim3(n_items), dim3(64), 0, c.stream, r);
+		else if (c.aux_depth) hipLaunchKernelGGL((k_render_fov<2, false, true>), dim3(n_items), dim3(64), 0, c.stream, r);
 		else hipLaunchKernelGGL((k_render_fov<2>), dim3(n_items), dim3(64), 0, c.stream, r);
 		break;
 	}

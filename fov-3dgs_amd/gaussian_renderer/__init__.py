@@ -109,8 +109,13 @@ def _reference_model_fields(pc):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, masking=False,
-           starter=None, ender=None, cuda_type="", loss_map=None, packed=None, want_stats=True, appearance_only=False):
+           starter=None, ender=None, cuda_type="", loss_map=None, packed=None, want_stats=True, appearance_only=False,
+           want_depth=False):
     """Render the scene. Background tensor (bg_color) must be on the GPU.
+    want_depth (extension, opt-in, cuda_type="pcheck_obb" only): the result gains "depth" and "coverage", [1,H,W] float32 each and
+    without gradient: over the (pixel, Gaussian) pairs the image accumulates, depth = sum of alpha T z (z: the Gaussian's view-space
+    depth) and coverage = 1 - the final transmittance. The background takes no part, a pixel no Gaussian reaches holds 0 in both,
+    and nothing is divided: the expected depth is depth / coverage.clamp_min(eps). Same image and radii as without the flag.
     packed (extension): a rasterizer.PackedModel of this (static) model made by pack_model(); same image, faster binning.
     want_stats (extension, opt-in): False = the caller does not read result["gs_count"] / ["contribs"] of the pcheck_obb_sum
     rasterizer (eff_finetune.py:107-108 drops them every step): the blend skips the per-Gaussian statistics and the two keys
@@ -121,6 +126,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     gradients; result["viewspace_points"] is a plain zero tensor without grad (nothing in the mask loop reads it). The raw-parameter
     and reference-model fast paths, which masking otherwise rules out, are taken again: the gradient arrives at the raw _opacity.
     A model that only offers the concatenated get_features_detach_rest is rendered as without the flag (one warning)."""
+    if want_depth and cuda_type != "pcheck_obb":
+        raise ValueError(f"want_depth: depth / coverage are outputs of the inference renderers \"pcheck_obb\" (this render()) and "
+                         f"\"fov_pcheck_obb\" (gaussian_renderer_fov.render()), not of cuda_type={cuda_type!r}")
     if appearance_only and not masking:
         raise ValueError("appearance_only is the backward pass of the masking step: call render(..., masking=True, appearance_only=True)")
     xyz = pc.get_xyz
@@ -195,6 +203,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     # i.e. with the raw parameters and split SH storage)
     if not want_stats and cuda_type == "pcheck_obb_sum":
         extra["want_stats"] = False
+    if want_depth:
+        extra["want_depth"] = True
     if appearance_only:
         if isinstance(shs, tuple):
             extra["appearance_only"] = True
@@ -222,4 +232,6 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
               "radii": out[1]}
     if len(out) == 4:
         result["gs_count"], result["contribs"] = out[2], out[3]
+    if want_depth:
+        result["depth"], result["coverage"] = out.depth, out.coverage
     return result

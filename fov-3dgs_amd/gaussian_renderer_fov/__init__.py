@@ -7,7 +7,7 @@ import torch
 
 from ..diff_gaussian_rasterization_fov_pcheck_obb import FoveationSettings, GaussianRasterizationSettings, GaussianRasterizer  # noqa: F401
 from .. import _native
-from ..rasterizer import PackedModel, _forward_begin, pack_model, serial_frames, visibility_of, zero_points_like
+from ..rasterizer import PackedModel, _forward_begin, depth_of, pack_model, serial_frames, visibility_of, zero_points_like
 
 
 class _PackState:
@@ -56,8 +56,14 @@ def _auto_packed(pc, means3D, scales, rotations, opacity, shs_rest, shs_dcs, hig
 
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, alpha=None, gazeArray=None,
            blending=None, starter=None, ender=None, highest_levels=None, shs_dcs=None, opacities=None, packed=None,
-           foveation=None, appearance_only=False, differentiable=False):
+           foveation=None, appearance_only=False, differentiable=False, want_depth=False):
     """Render the scene for one gaze. Background tensor (bg_color) must be on the GPU.
+    want_depth (extension, opt-in, inference): the result gains "depth" and "coverage", [1,H,W] float32 each and without gradient --
+    what a compositor merges the frame with its other layers by and reprojects it with. They are the blend's own quantities: over
+    the (pixel, Gaussian) pairs the image accumulates, depth = sum of alpha T z (z: the Gaussian's view-space depth) and coverage =
+    1 - the final transmittance; in a two-level tile both are mixed with the image's two shares. The background takes no part, a
+    pixel no Gaussian reaches holds 0 in both, and nothing is divided: the expected depth is depth / coverage.clamp_min(eps). The
+    image and radii are those of the call without the flag, bit for bit. Refused together with appearance_only / differentiable.
     differentiable (extension, opt-in): with autograd on, the image is differentiable in everything a fine-tune step of the composed
     model moves -- pc.get_xyz, get_scaling, get_rotation, get_rest_features and the per-level `shs_dcs` [P,L,3] / `opacities` [P,L]
     (fr_backward_fov; at most 4 layers) -- and "viewspace_points".grad is populated as the plain renderer populates it (what
@@ -79,6 +85,9 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
     bypass the version counter (`t.data.copy_()`, raw-pointer kernels, DLPack aliases): call invalidate_packed(pc) after
     such a write."""
     xyz = pc.get_xyz
+    if want_depth and (appearance_only or differentiable):
+        raise ValueError("want_depth: depth / coverage are outputs of the inference frame, not of the state-keeping forwards "
+                         "(appearance_only / differentiable)")
     if differentiable:
         if appearance_only:
             raise ValueError("differentiable and appearance_only exclude each other: appearance_only detaches what differentiable trains")
@@ -147,13 +156,17 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, a
             means3D=means3D, means2D=means2D, shs_rest=shs_rest, colors_precomp=None, opacities=opacity, scales=scales,
             rotations=rotations, cov3D_precomp=None, shs_dcs=shs_dcs, highest_levels=highest_levels,
             gazeArray=gazeArray, alpha=alpha, blending=blending, packed=packed, foveation=foveation,
-            **({"appearance_only": True} if appearance_only else {}), **({"differentiable": True} if differentiable else {}))
+            **({"appearance_only": True} if appearance_only else {}), **({"differentiable": True} if differentiable else {}),
+            **({"want_depth": True} if want_depth else {}))
     if ender is not None:
         ender.record()
 
     # (`radii > 0` as the kernels that write the radii left it: no pass of torch's over the radii behind the frame)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visibility_of(radii),
-            "radii": radii}
+    result = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visibility_of(radii),
+              "radii": radii}
+    if want_depth:
+        result["depth"], result["coverage"] = depth_of(radii)
+    return result
 
 
 class PendingRender:

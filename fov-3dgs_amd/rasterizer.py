@@ -366,14 +366,41 @@ _bwd_events_hook = None  # the same for backward calls: 5 handles (fr_backward_a
 class RasterOutput(tuple):
     """What GaussianRasterizer.__call__ returns: the reference's tuple -- (color, radii[, gaussians_count, contributions]) --
     with one attribute beside it: visibility_filter, the [P] bool tensor `radii > 0` as the kernels that write the radii wrote
-    it (fr_forward_ext.visibility), or None when the loaded library does not write it (the renderers then compute it)."""
+    it (fr_forward_ext.visibility), or None when the loaded library does not write it (the renderers then compute it).
+    depth / coverage: the [1,H,W] float32 planes of a call with want_depth=True (fr_forward_aux), else None."""
     visibility_filter = None
+    depth = None
+    coverage = None
 
 
 def _raster_output(out):
     res = RasterOutput(out)
     res.visibility_filter = getattr(out[1], "_fovraster_visibility", None)
+    res.depth, res.coverage = depth_of(out[1])
     return res
+
+
+def depth_of(radii):
+    """(depth, coverage) of a call with want_depth=True, from its radii tensor (they travel as the visibility mask does), else (None, None)"""
+    return getattr(radii, "_fovraster_depth", None), getattr(radii, "_fovraster_coverage", None)
+
+
+# Test switch: the two planes of a want_depth call hold NaN before the native call instead of whatever the allocator had (a pixel the
+# library fails to write -- it writes every one -- then shows in any comparison).
+POISON_DEPTH_OUTPUTS = False
+
+
+def _aux_planes(lib, radii, H, W, dev):
+    """the freshly allocated depth / coverage planes of a want_depth call as attributes of `radii`, and the call's _native.ForwardAux"""
+    if not _native.has_forward_aux(lib):
+        raise RuntimeError("fovraster: the loaded library has no depth / coverage outputs (fr_forward_begin_aux): rebuild it")
+    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)  # both written in full by the call
+    coverage = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    if POISON_DEPTH_OUTPUTS:
+        depth.fill_(float("nan"))
+        coverage.fill_(float("nan"))
+    radii._fovraster_depth, radii._fovraster_coverage = depth, coverage
+    return _native.ForwardAux(C.sizeof(_native.ForwardAux), depth.data_ptr(), coverage.data_ptr())  # (read during the call only)
 
 
 def visibility_of(radii):
@@ -382,21 +409,26 @@ def visibility_of(radii):
     return vis if vis is not None else radii > 0
 
 
-def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None, keep_full=False):
+def _begin_call(lib, a, P, dev, radii, handle, fov=None, keep_state=None, keep_full=False, aux=None):
     """fr_forward_begin with the visibility mask as a second output where the library has it: the mask travels as an attribute of
     `radii`, through the result tuples and autograd (a non-differentiable output keeps its Python object).
     fov: the call's _native.Foveation (_foveation_struct), or None = today's entry points.
     keep_state: a _native.FovState = the state-keeping foveated forward (fr_forward_begin_fov_keep), which fills it at finish;
-    keep_full: ... for the full backward pass (fr_forward_begin_fov_keep_full: a larger geometry workspace)."""
+    keep_full: ... for the full backward pass (fr_forward_begin_fov_keep_full: a larger geometry workspace).
+    aux: the call's _native.ForwardAux (_aux_planes: want_depth=True), or None = today's entry points."""
     if keep_state is not None and keep_full and not _native.has_fov_full_backward(lib):
         raise RuntimeError("fovraster: the loaded library has no full foveated backward pass (fr_backward_fov): rebuild it")
     if keep_state is not None and not _native.has_fov_backward(lib):
         raise RuntimeError("fovraster: the loaded library has no foveated backward pass (fr_backward_fov_appearance): rebuild it")
     if not _native.has_forward_ext(lib):
+        if aux is not None:
+            raise RuntimeError("fovraster: the loaded library has no optional outputs (fr_forward_begin_ext): rebuild it")
         return lib.fr_forward_begin(C.byref(a), C.byref(handle))
     vis = torch.empty((P,), dtype=torch.bool, device=dev)  # written in full beside radii, like it
     radii._fovraster_visibility = vis
     ext = _native.ForwardExt(C.sizeof(_native.ForwardExt), vis.data_ptr())  # (read during the call only)
+    if aux is not None:
+        return lib.fr_forward_begin_aux(C.byref(a), C.byref(ext), C.byref(fov) if fov is not None else None, C.byref(aux), C.byref(handle))
     if keep_state is not None:
         begin = lib.fr_forward_begin_fov_keep_full if keep_full else lib.fr_forward_begin_fov_keep
         return begin(C.byref(a), C.byref(ext), C.byref(fov) if fov is not None else None, C.byref(keep_state),
@@ -448,7 +480,8 @@ class FrameInFlight:
 def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                    shs_dcs=None, highest_levels=None, gaze=(0.5, 0.5), alpha=0.05, persistent=False, loss_map=None,
                    sh_rest=None, packed=None, cur_level=0.0, raw_activations=False, list_consumed=None, no_stats=False, blend_pairs=None,
-                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False, keep_state=None, keep_full=False):
+                   on_stream=None, reuse=None, reuse_key=None, foveation=None, count=False, keep_state=None, keep_full=False,
+                   want_depth=False):
     """First half of a forward call on the current stream -> FrameInFlight. count (variant original only): the counting render of
     LightGaussian's global-significance pruning -- the call also returns gaussians_count (exact hits per Gaussian) and the
     important_score (fovraster.h, fr_forward_args.gaussians_count); image and radii are those of the plain call.
@@ -464,8 +497,13 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
     foveation (foveated variant): a FoveationSettings, or None = the reference's constants through the entry points without settings.
     keep_state (foveated variant, training): a _native.FovState with its size set -- the state-keeping forward: the frame also keeps
     what fr_backward_fov_appearance needs and fills the struct at finish() (the caller keeps it, and the workspaces, until backward);
-    keep_full: what fr_backward_fov needs (the full backward pass)."""
+    keep_full: what fr_backward_fov needs (the full backward pass).
+    want_depth (pcheck_obb and the foveated variant, inference): the call also writes the per-pixel depth and coverage planes
+    (fr_forward_aux), allocated here per call and handed on as attributes of the radii tensor (depth_of); part of reuse_key (the
+    caller's), so an argument struct is only used again by a frame of the same kind."""
     lib = _native.load()
+    if want_depth and not _native.has_forward_aux(lib):
+        raise RuntimeError("fovraster: the loaded library has no depth / coverage outputs (fr_forward_begin_aux): rebuild it")
     _require_gpu(means3D)
     dev = means3D.device
     P = means3D.size(0)
@@ -480,12 +518,14 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         a.out_color, a.radii = color.data_ptr(), radii.data_ptr()
         a.stage_events = _stage_events_hook() if _stage_events_hook is not None else None
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle, reuse["fov"])
+        rc = _begin_call(lib, a, P, dev, radii, handle, reuse["fov"], None, False, _aux_planes(lib, radii, H, W, dev) if want_depth else None)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
         return FrameInFlight(lib, a, keep, color, radii, ws, None, None, None, handle, dev, stream)
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if want_depth and (variant not in (_native.VARIANT_FOV_PCHECK_OBB, _native.VARIANT_PCHECK_OBB) or keep_state is not None):
+        raise RuntimeError("fovraster: depth / coverage are outputs of the inference renderers fov_pcheck_obb and pcheck_obb only")
     fov_key = _foveation_key(foveation)
     if fov_key is not None and variant != _native.VARIANT_FOV_PCHECK_OBB:
         raise RuntimeError("fovraster: foveation settings are for the foveated rasterizer (fov_pcheck_obb) only")
@@ -584,7 +624,8 @@ def _forward_begin(variant, rs, means3D, sh, colors_precomp, opacities, scales, 
         if _stage_events_hook is not None:
             a.stage_events = _stage_events_hook()
         handle = C.c_void_p()
-        rc = _begin_call(lib, a, P, dev, radii, handle, fov, keep_state, keep_full)
+        rc = _begin_call(lib, a, P, dev, radii, handle, fov, keep_state, keep_full,
+                         _aux_planes(lib, radii, H, W, dev) if want_depth else None)
         if rc != 0:
             raise RuntimeError(f"fovraster forward failed ({rc}): {_native.last_error()}")
         if keep_state is not None:
@@ -725,7 +766,7 @@ def _forward_overlapped(args, kw):
             done.record(own)
     st.done[i] = done
     cur.wait_event(done)  # everything the caller enqueues from here on sees the finished frame
-    for t in res + (getattr(res[2], "_fovraster_visibility", None),):
+    for t in res + (getattr(res[2], "_fovraster_visibility", None),) + depth_of(res[2]):
         if isinstance(t, torch.Tensor) and t.is_cuda:
             t.record_stream(cur)
     return res
@@ -1204,7 +1245,14 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
 
     def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                             raster_settings, loss_map=None, sh_rest=None, packed=None, raw_activations=False, row_sparse=False,
-                            want_stats=True, appearance_only=False):
+                            want_stats=True, appearance_only=False, want_depth=False):
+        if want_depth:
+            # (pcheck_obb, inference-only: there is no graph to build; the call below is _RasterizeGaussians.forward's with the two planes)
+            if sh_rest is not None and sh_rest.numel() == 0:
+                sh_rest = None
+            res = _forward_begin(variant_id, raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                 persistent=True, sh_rest=sh_rest, packed=packed, raw_activations=raw_activations, want_depth=True).finish()
+            return res[1], res[2]
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, raster_settings, loss_map if takes_loss_map else None, sh_rest, packed,
                                          torch.is_grad_enabled(), raw_activations, row_sparse, want_stats, appearance_only)
@@ -1220,8 +1268,14 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
 
         def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                     cov3D_precomp=None, loss_map=None, packed=None, raw_activations=False, row_sparse=False, want_stats=True,
-                    appearance_only=False):
+                    appearance_only=False, want_depth=False):
+            """want_depth (extension, pcheck_obb only): the result also carries .depth and .coverage, [1,H,W] float32 each, without
+            gradient: depth = sum of alpha T z over the pairs the image blends (z: view-space depth), coverage = 1 - the final
+            transmittance; the background takes no part and an untouched pixel holds 0 in both. Nothing is divided: the expected depth
+            is depth / coverage.clamp_min(eps)."""
             raster_settings = self.raster_settings
+            if want_depth and variant_id != _native.VARIANT_PCHECK_OBB:
+                raise ValueError("want_depth: depth / coverage are outputs of the inference renderers pcheck_obb and fov_pcheck_obb only")
             if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
                 raise Exception('Please provide excatly one of either SHs or precomputed colors!')
             if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -1245,7 +1299,7 @@ def _make_plain(variant_id, with_counts, has_backward, takes_loss_map=False):
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, loss_map, shs_rest, packed, raw_activations, row_sparse, want_stats,
-                                       appearance_only))
+                                       appearance_only, want_depth))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 
@@ -1351,7 +1405,13 @@ def _make_fov():
 
     def rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha, blending,
-                            packed=None, foveation=None, appearance_only=False, differentiable=False):
+                            packed=None, foveation=None, appearance_only=False, differentiable=False, want_depth=False):
+        if want_depth:
+            # (the inference frame with the two planes; they carry no gradient and neither does the image of such a call)
+            res = _forward_native(variant_id, raster_settings, means3D, shs_rest, colors_precomp, opacities, scales, rotations,
+                                  cov3Ds_precomp, shs_dcs, highest_levels, _gaze_pair(gazeArray), float(alpha), persistent=True, packed=packed,
+                                  foveation=foveation, want_depth=True)
+            return res[1], res[2]
         if not torch.is_grad_enabled() and not raster_settings.debug:
             # (inference: no graph to build -- the autograd machinery around an inference-only extension is 15 us of host time a
             # frame on a path where the host sets the pace, see OVERLAP_SUCCESSIVE_FRAMES)
@@ -1374,8 +1434,13 @@ def _make_fov():
 
         def forward(self, means3D, means2D, opacities, shs_rest=None, colors_precomp=None, scales=None,
                     rotations=None, cov3D_precomp=None, shs_dcs=None, highest_levels=None, gazeArray=None,
-                    alpha=None, blending=None, packed=None, foveation=None, appearance_only=False, differentiable=False):
-            """foveation (extension): a FoveationSettings -- layer count and display geometry --, or None = the reference's
+                    alpha=None, blending=None, packed=None, foveation=None, appearance_only=False, differentiable=False,
+                    want_depth=False):
+            """want_depth (extension, inference): the result also carries .depth and .coverage, [1,H,W] float32 each, without gradient:
+            depth = sum of alpha T z over the pairs the image blends (z: view-space depth), coverage = 1 - the final transmittance, in a
+            two-level tile both mixed with the image's shares; the background takes no part and an untouched pixel holds 0 in both.
+            Nothing is divided: the expected depth is depth / coverage.clamp_min(eps). Not with appearance_only / differentiable.
+            foveation (extension): a FoveationSettings -- layer count and display geometry --, or None = the reference's
             constants (4 layers, maximum pooling size 12, a display 2 wide seen from 1, blend band 0.5 / 0.5).
             appearance_only (extension, opt-in): with autograd on, the image is differentiable in opacities [P,L] and shs_dcs [P,L,3]
             (fr_backward_fov_appearance; at most 4 layers); every other input gets None, and one that requires grad is refused. Without
@@ -1384,6 +1449,9 @@ def _make_fov():
             points), scales, rotations, shs_rest, opacities [P,L] and shs_dcs [P,L,3] (fr_backward_fov; at most 4 layers); needs
             scales / rotations and shs_rest (no precomputed covariance or colours); highest_levels must not require grad."""
             raster_settings = self.raster_settings
+            if want_depth and (appearance_only or differentiable):
+                raise ValueError("want_depth: depth / coverage are outputs of the inference frame, not of the state-keeping forwards "
+                                 "(appearance_only / differentiable)")
             if differentiable:
                 if appearance_only:
                     raise ValueError("differentiable and appearance_only exclude each other: appearance_only detaches what differentiable trains")
@@ -1413,7 +1481,7 @@ def _make_fov():
             cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
             return _raster_output(rasterize_gaussians(means3D, means2D, shs_rest, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, raster_settings, shs_dcs, highest_levels, gazeArray, alpha,
-                                       blending, packed, foveation, appearance_only, differentiable))
+                                       blending, packed, foveation, appearance_only, differentiable, want_depth))
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 

@@ -343,6 +343,34 @@ typedef struct fr_foveation {
 } fr_foveation;
 int fr_forward_begin_fov(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, fr_frame **frame);
 int fr_forward_fov_call(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov);
+/* Per-pixel depth and coverage of the two INFERENCE renderers, FR_VARIANT_FOV_PCHECK_OBB and FR_VARIANT_PCHECK_OBB (extension; the
+ * reference has neither: what a compositor merges the frame with its other layers by, and reprojects it with). The quantities are the
+ * blend's own: a (pixel, Gaussian j) pair takes part exactly when the colour blend accumulates it (the same support test, the same
+ * alpha < 1/255 test, the same T (1 - alpha) < 1e-4 stop; the stopping entry is not accumulated). With w_j = alpha_j T_j and z_j the
+ * Gaussian's view-space depth (the float whose bits are in the sort key):
+ *   depth    [H*W]  sum_j w_j z_j
+ *   coverage [H*W]  1 - T_end (the transmittance the pixel ended with)
+ *   a two-level tile of the foveated renderer: s1 D1 + s2 D2 and s1 (1 - T1) + s2 (1 - T2) with the shares s1 = w1, s2 = 1 - w1 of
+ *   the image (w1 = 1 - smoothstep); a state-1 pixel that starts finished adds nothing, the upper state skips what does not exist at
+ *   its level. The two rounded halves meet by float atomicAdd on a cleared pixel (x + y == y + x: no dependence on the order).
+ * The background takes no part; a pixel no Gaussian reaches holds depth = 0 and coverage = 0. Nothing is divided: the EXPECTED depth
+ * is the caller's depth / max(coverage, eps). Both planes are caller-allocated and written in full by the call (no initialisation
+ * needed): every pixel by the blend -- a second instantiation of the blend kernel, launched only by these entry points; the image and
+ * radii are those of the call without the outputs bit for bit --, and the two-level tiles of a foveated frame are cleared first by a
+ * small tile-wise kernel behind the tile levels (no fill command over the planes). size = sizeof(fr_forward_aux) as the caller was
+ * compiled; the struct is read during the begin call only.
+ * fr_forward_begin_aux / fr_forward_aux_call are fr_forward_begin_fov / fr_forward_fov_call with these outputs; aux == NULL (or both
+ * pointers NULL): the same calls. packed_* inputs, fr_foveation with any legal level count, every value of no_helper_streams and
+ * list_consumed / blend_pairs work beside them. FR_ERR_INVALID before anything is enqueued, the message names the cause: size too
+ * small; exactly one of the two pointers set; a variant other than the two above. (The state-keeping forwards take no fr_forward_aux:
+ * their entry points have no such argument, and the library's common begin path refuses the pair.) */
+typedef struct fr_forward_aux {
+	uint32_t size;
+	float *depth;
+	float *coverage;
+} fr_forward_aux;
+int fr_forward_begin_aux(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, const fr_forward_aux *aux, fr_frame **frame);
+int fr_forward_aux_call(fr_forward_args *args, const fr_forward_ext *ext, const fr_foveation *fov, const fr_forward_aux *aux);
 /* Fill fr_forward_args.packed_geom / packed_colour / packed_cull (device buffers of P*16 / P*64 / P*4 floats) from the tensors of the
  * same names; opacities is [P,levels] with levels = 1 or 4, highest_levels / shs_dcs may be NULL (not RF);
  * shs_rest NULL: shs is [P,16,3] (RF: [P,15,3] = coefficients 1..15 and shs_dcs given), else shs = [P,1,3]. */
