@@ -80,12 +80,14 @@ class QualityMeter:
         return bool(r["psnr"] >= target_psnr) and bool(r["ssim"] >= target_ssim)
 
 
-def evaluate_views(model, cameras, pipe, bg, render=None, hvs=None, resize="pyramid"):
+def evaluate_views(model, cameras, pipe, bg, render=None, hvs=None, resize="pyramid", lpips=None):
     """prune.py's test_ssim_loss and test_psnr_loss (:137-174) in one loop with ONE render per camera
     (``cuda_type="pcheck_obb"``, under no_grad) against ``camera.original_image``, and with ``hvs=`` a MetamericLossUniform also
     metric_mask_learn.py's test_hvs_loss (:120-135), the resize to the pyramid's size done inside its kernels (``resize=``).
     `render` defaults to fov3dgs_amd.gaussian_renderer.render. Returns QualityMeter.result(), plus "hvs" (the mean) and
-    per_view["hvs"] when asked. Nothing synchronises with the host between the first render and the readback."""
+    per_view["hvs"] when asked, and with ``lpips=`` an lpipsPyTorch.LPIPS object also "lpips" (the mean) and per_view["lpips"],
+    the fourth figure of the reference's tables (quality_metrics.py:61-83, hvs_metrics.py:71-98: lpips(render, gt, net_type='vgg')). Nothing synchronises with the
+    host between the first render and the readback."""
     if render is None:
         from .gaussian_renderer import render
     cameras = list(cameras)
@@ -97,6 +99,7 @@ def evaluate_views(model, cameras, pipe, bg, render=None, hvs=None, resize="pyra
     dev = xyz.device
     meter = QualityMeter(dev, len(cameras))
     hvs_vals = torch.zeros(len(cameras), dtype=torch.float32, device=dev) if hvs is not None else None
+    lpips_vals = torch.zeros(len(cameras), dtype=torch.float32, device=dev) if lpips is not None else None
     with torch.no_grad():
         for v, cam in enumerate(cameras):
             image = render(cam, model, pipe, bg, cuda_type="pcheck_obb")["render"]
@@ -104,9 +107,15 @@ def evaluate_views(model, cameras, pipe, bg, render=None, hvs=None, resize="pyra
             meter.add(image, gt)
             if hvs is not None:
                 hvs_vals[v] = hvs(image.unsqueeze(0), gt.unsqueeze(0), resize=resize)
+            if lpips is not None:
+                lpips_vals[v] = lpips(image.unsqueeze(0), gt.unsqueeze(0)).reshape(())
     out = meter.result()
     if hvs is not None:
         per = hvs_vals.cpu()
         out["per_view"]["hvs"] = per
         out["hvs"] = float(per.double().mean())
+    if lpips is not None:
+        per = lpips_vals.cpu()
+        out["per_view"]["lpips"] = per
+        out["lpips"] = float(per.double().mean())
     return out

@@ -1000,6 +1000,54 @@ const uint32_t *fr_geometry_level_ranges(int32_t P, const char *geometry);
  * levels 0 .. 3); NULL for levels <= 4 */
 const float *fr_geometry_level_colours_hi(int32_t P, int32_t levels, const char *geometry);
 
+/* LPIPS, VGG16, version 0.1 (csrc/lpips.hip; replaces fov3dgs/lpipsPyTorch/__init__.py:6-21, modules/lpips.py:30-36,
+ * modules/networks.py:41-64 and :89-96, modules/utils.py:6-8 -- a torchvision VGG16 and two weight downloads per picture pair).
+ * The library holds no weights: the caller hands in the 13 convolutions of vgg16().features and the five `lin` vectors.
+ *   fr_lpips_packed_bytes     the size of the packed weights.
+ *   fr_lpips_pack_weights     a HOST routine, once per set of weights: conv_weights[13] ([Cout,Cin,3,3] each, the convolutions of
+ *                             vgg16().features in order: 3-64, 64-64, 64-128, 128-128, 128-256, 256-256 x2, 256-512, 512-512 x5),
+ *                             conv_biases[13] ([Cout]) and lin_weights[5] ([C], C = 64, 128, 256, 512, 512), all host float32, into
+ *                             `packed` (host, fr_lpips_packed_bytes). The caller copies `packed` to the device. A NULL pointer is
+ *                             FR_ERR_INVALID, the message names it.
+ *   fr_lpips_workspace_bytes  the workspace of one call over N picture pairs of H x W: two ping-pong activation buffers of
+ *                             2 N x 64 x H x W floats (relu1_1 and relu1_2 of both pictures, the largest maps) and the head's
+ *                             partial sums; -1 for sizes fr_lpips_forward refuses (fr_last_error says which).
+ *   fr_lpips_forward          size = sizeof(fr_lpips_args). x, y: [N,3,H,W] fp32 device planes, scaled as the caller has them
+ *                             ((x - mean) / std is applied on load; [0, 1] pictures are NOT rescaled to [-1, 1], as in the
+ *                             reference). packed: the packed weights on the device, 16-byte aligned. workspace: 256-byte aligned.
+ *                             out[1] (device) = sum over the five taps AND over the batch of mean_HW( sum_c w_c (n(fx)_c -
+ *                             n(fy)_c)^2 ), n(a) = a / (sqrt(sum_c a_c^2) + 1e-10): torch.sum(torch.cat(res, 0), 0, True) of the
+ *                             reference. out_taps (optional, device [5]): the five addends, each summed over the batch.
+ *                             out_features[k] (optional, device [N,C_k,H_k,W_k], NCHW): x's tap maps before the normalisation
+ *                             (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; H_k = H >> k), for tests and diagnosis.
+ *                             Exact f32 on the matrix cores, one k-ordered chain per output, sums in double in a fixed order, no
+ *                             float atomics: every output is one bit pattern, run after run; equal pictures give exactly 0.
+ *                             stage_events (optional [19], fr_event_create handles, NULL entries skipped): recorded on `stream` in
+ *                             front of the first layer ([0]) and behind each of the 18 stages in their order -- the 13
+ *                             convolutions, the head of a tap directly behind the tap's convolution.
+ *                             Everything runs on `stream`; nothing is allocated and nothing synchronises (debug != 0 does, after
+ *                             every stage). FR_ERR_INVALID before anything is enqueued, the message names the field: size too
+ *                             small, N outside 1 .. 512, H or W outside 16 .. 16384 (below 16 the fourth pool has no output: the
+ *                             reference raises there too), x / y / packed / workspace / out NULL, a misaligned buffer. */
+typedef struct fr_lpips_args {
+	uint32_t size;
+	int32_t N, H, W;
+	int32_t debug;
+	const float *x;
+	const float *y;
+	const void *packed;
+	void *workspace;
+	float *out;
+	float *out_taps;
+	float *out_features[5];
+	void *stream;
+	void **stage_events;
+} fr_lpips_args;
+size_t fr_lpips_packed_bytes(void);
+int fr_lpips_pack_weights(const float *const *conv_weights, const float *const *conv_biases, const float *const *lin_weights, void *packed);
+int64_t fr_lpips_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int fr_lpips_forward(const fr_lpips_args *args);
+
 #ifdef __cplusplus
 }
 #endif
