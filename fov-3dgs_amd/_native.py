@@ -131,6 +131,20 @@ class LpipsArgs(C.Structure):
                 ("out_features", _FP * 5), ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p))]
 
 
+class LpipsKeepArgs(C.Structure):
+    """fr_lpips_keep_args"""
+    _fields_ = [("size", C.c_uint32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("debug", C.c_int32),
+                ("x", _FP), ("y", _FP), ("packed", _FP), ("workspace", _FP), ("keep", _FP), ("out", _FP), ("out_taps", _FP),
+                ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p))]
+
+
+class LpipsBackwardArgs(C.Structure):
+    """fr_lpips_backward_args"""
+    _fields_ = [("size", C.c_uint32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("debug", C.c_int32),
+                ("packed_backward", _FP), ("keep", _FP), ("workspace", _FP), ("grad_out", _FP), ("grad_x", _FP),
+                ("stream", C.c_void_p), ("stage_events", C.POINTER(C.c_void_p))]
+
+
 ADAM_MAX_TENSORS = 16
 ADAM_DENSE, ADAM_EXACT, ADAM_LAZY = 0, 1, 2
 
@@ -205,7 +219,9 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_image_fov_state_T", "fr_image_fov_state_n", "fr_backward_fov_appearance",
            "fr_forward_begin_fov_keep_full", "fr_forward_fov_keep_full_call", "fr_geometry_bytes_fov_keep_full", "fr_backward_fov",
            "fr_forward_begin_aux", "fr_forward_aux_call",
-           "fr_lpips_packed_bytes", "fr_lpips_pack_weights", "fr_lpips_workspace_bytes", "fr_lpips_forward")
+           "fr_lpips_packed_bytes", "fr_lpips_pack_weights", "fr_lpips_workspace_bytes", "fr_lpips_forward",
+           "fr_lpips_backward_packed_bytes", "fr_lpips_pack_backward_weights", "fr_lpips_keep_workspace_bytes",
+           "fr_lpips_keep_activation_offset", "fr_lpips_forward_keep", "fr_lpips_backward")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -443,6 +459,18 @@ def load():
     lib.fr_lpips_workspace_bytes.restype = C.c_int64
     lib.fr_lpips_forward.argtypes = [C.POINTER(LpipsArgs)]
     lib.fr_lpips_forward.restype = C.c_int
+    lib.fr_lpips_backward_packed_bytes.argtypes = []
+    lib.fr_lpips_backward_packed_bytes.restype = C.c_size_t
+    lib.fr_lpips_pack_backward_weights.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
+    lib.fr_lpips_pack_backward_weights.restype = C.c_int
+    lib.fr_lpips_keep_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.fr_lpips_keep_workspace_bytes.restype = C.c_int64
+    lib.fr_lpips_keep_activation_offset.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.fr_lpips_keep_activation_offset.restype = C.c_int64
+    lib.fr_lpips_forward_keep.argtypes = [C.POINTER(LpipsKeepArgs)]
+    lib.fr_lpips_forward_keep.restype = C.c_int
+    lib.fr_lpips_backward.argtypes = [C.POINTER(LpipsBackwardArgs)]
+    lib.fr_lpips_backward.restype = C.c_int
     if lib.fr_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"fovraster: ABI version mismatch ({lib.fr_abi_version()} != {ABI_VERSION})")
     _lib = lib

@@ -32,6 +32,16 @@
 //                           total into the call's scalar.
 // Activations are kept as [image][C / 8][H][W][8] (x's pictures, then y's): a chunk of a halo row is one contiguous run, and a
 // lane's four accumulator registers are one 16-byte store. Two buffers ping-pong; tap k's head runs before its buffer is reused.
+//
+// As a training loss (the reference's nn.Module under torch.autograd: lpips(render, gt).backward()):
+//   fr_lpips_forward_keep   the same kernels, x's 13 post-ReLU maps written to a caller-owned kept state instead of ping-ponging
+//                           (y's still ping-pong), and k_lpips_head<true>: the head also writes the gradient of the tap's value with
+//                           respect to x's tap map, scaled by 1 / (H_k W_k), while both pictures' taps are in hand -- chosen over
+//                           keeping y's five taps for the backward: the same bytes kept, one pass over them less.
+//   fr_lpips_backward       layers 12 .. 1: k_lpips_conv's main loop on the transposed, flipped weights with the epilogues
+//                           LP_EPI_MASK (the ReLU rule) and LP_EPI_POOL_TAP (pool scatter to the first maximum + the tap's own
+//                           gradient + the ReLU rule, behind the four pooled taps); then k_lpips_conv0_bwd, 64 -> 3, 1 / std and
+//                           the upstream scalar, read on the device. The gradient at a layer's output ping-pongs in the workspace.
 #include "common.h"
 #include <math.h>
 #include <string.h>
@@ -85,6 +95,35 @@ static LpWorkspace lp_workspace(int N, int H, int W)
 	return L;
 }
 
+// the differentiable forward's kept state: x's 13 post-ReLU maps in the convolution's layout, and the five tap gradients
+// (d value / d tap map of x, k_lpips_head<true>) in the same layout. y's maps are not kept.
+struct LpKeep { size_t act[LP_LAYERS], tg[LP_TAPS], bytes; };
+static int lp_layer_shift(int l) { return l < 2 ? 0 : l < 4 ? 1 : l < 7 ? 2 : l < 10 ? 3 : 4; } // pools in front of layer l
+static LpKeep lp_keep(int N, int H, int W)
+{
+	LpKeep K; size_t off = 0;
+	for (int l = 0; l < LP_LAYERS; l++)
+	{
+		K.act[l] = off; off = align_up(off + (size_t)N * lp_cout[l] * (H >> lp_layer_shift(l)) * (W >> lp_layer_shift(l)) * 4);
+	}
+	for (int k = 0; k < LP_TAPS; k++)
+	{
+		K.tg[k] = off; off = align_up(off + (size_t)N * lp_tap_c[k] * (H >> k) * (W >> k) * 4);
+	}
+	K.bytes = off;
+	return K;
+}
+
+// backward weights, in floats: the first layer's [chunk][tap][8][3], then the slabs of the layers 1 .. 12
+struct LpBackPacked { size_t w[LP_LAYERS], floats; };
+static LpBackPacked lp_back_packed()
+{
+	LpBackPacked P; size_t off = 0;
+	for (int l = 0; l < LP_LAYERS; l++) { P.w[l] = off; off += (size_t)9 * lp_cin[l] * lp_cout[l]; }
+	P.floats = off;
+	return P;
+}
+
 static bool lp_sizes_ok(int N, int H, int W) { return N >= 1 && N <= LP_MAX_N && H >= 16 && W >= 16 && H <= LP_MAX_HW && W <= LP_MAX_HW; }
 
 // ---- first layer: 3 -> 64, z-score on load --------------------------------------------------------------------------------
@@ -133,9 +172,27 @@ __global__ void __launch_bounds__(256) k_lpips_conv0(int H, int W, const float *
 // grid (tiles across, tiles down, images * Cout / 64). The MFMA's A operand is the weights (row = output channel l & 15, k = l >> 4),
 // its B operand the pixels (k = l >> 4, column = pixel l & 15 of a row of the tile): lane l then holds D[row 4 (l >> 4) + q][column
 // l & 15], four consecutive output channels of one pixel. Both operands are read from LDS as 64 consecutive words (no bank conflict).
+//
+// The backward pass runs the same main loop on the transposed, flipped weights (fr_lpips_pack_backward_weights; no bias) with one
+// of two other epilogues. `act` is the kept post-ReLU map the gradient arrives at, in the layout of `out`:
+//   LP_EPI_MASK      out = sum * (act > 0): the ReLU rule, for a layer that no pool follows.
+//   LP_EPI_POOL_TAP  H x W is the POOLED size, act / tapgrad / out are the tap map in front of the pool, Ht x Wt. A pooled value
+//                    goes to the first maximum of its 2 x 2 window in row-major order (torch's `val > maxval`), zero to the other
+//                    three; the tap's own gradient is added at all four and the sum is masked by act > 0. The row Ht - 1 of an odd
+//                    Ht lies in no window: the lane that owns the pooled pixel (H - 1, gx) writes tapgrad * mask at (Ht - 1, 2 gx)
+//                    and (Ht - 1, 2 gx + 1); likewise the column Wt - 1 of an odd Wt by the owner of (gy, W - 1), and the corner
+//                    (Ht - 1, Wt - 1) by the owner of (H - 1, W - 1). Every pooled pixel has exactly one owner per channel, so
+//                    every element of the tap map is written exactly once.
+// The masks are selections, not products: a gradient at a dead activation is dropped whatever its value.
+enum { LP_EPI_RELU = 0, LP_EPI_MASK = 1, LP_EPI_POOL_TAP = 2 };
 typedef float lp_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 lp_mask(const float4 a, const float4 v)
+{
+	return make_float4(a.x > 0.0f ? v.x : 0.0f, a.y > 0.0f ? v.y : 0.0f, a.z > 0.0f ? v.z : 0.0f, a.w > 0.0f ? v.w : 0.0f);
+}
+template <int EPI>
 __global__ void __launch_bounds__(256) k_lpips_conv(int H, int W, int Cin, int Cout, const float *__restrict__ in, const float *__restrict__ wp,
-	const float *__restrict__ bias, float *__restrict__ out)
+	const float *__restrict__ bias, float *__restrict__ out, const float *__restrict__ act, const float *__restrict__ tapgrad, int Ht, int Wt)
 {
 	__shared__ __attribute__((aligned(16))) float wl[LP_SLAB];
 	__shared__ __attribute__((aligned(16))) float il[2 * LP_NPIX * 4];
@@ -209,27 +266,92 @@ __global__ void __launch_bounds__(256) k_lpips_conv(int H, int W, int Cin, int C
 	for (int mt = 0; mt < 4; mt++)
 	{
 		const int co = ob * 64 + mt * 16 + 4 * h; // this lane's four consecutive output channels
-		const float4 bv = *(const float4 *)(bias + co);
-#pragma unroll
-		for (int r = 0; r < 4; r++)
+		if constexpr (EPI == LP_EPI_RELU)
 		{
-			const int gy = ty0 + wave * 4 + r;
-			if (gy >= H) continue;
-			float4 o;
-			o.x = fmaxf(tot[mt][r][0] + bv.x, 0.0f); o.y = fmaxf(tot[mt][r][1] + bv.y, 0.0f);
-			o.z = fmaxf(tot[mt][r][2] + bv.z, 0.0f); o.w = fmaxf(tot[mt][r][3] + bv.w, 0.0f);
-			*(float4 *)(out + (((size_t)img * (Cout >> 3) + (co >> 3)) * plane + (size_t)gy * W + gx) * 8 + (co & 7)) = o;
+			const float4 bv = *(const float4 *)(bias + co);
+#pragma unroll
+			for (int r = 0; r < 4; r++)
+			{
+				const int gy = ty0 + wave * 4 + r;
+				if (gy >= H) continue;
+				float4 o;
+				o.x = fmaxf(tot[mt][r][0] + bv.x, 0.0f); o.y = fmaxf(tot[mt][r][1] + bv.y, 0.0f);
+				o.z = fmaxf(tot[mt][r][2] + bv.z, 0.0f); o.w = fmaxf(tot[mt][r][3] + bv.w, 0.0f);
+				*(float4 *)(out + (((size_t)img * (Cout >> 3) + (co >> 3)) * plane + (size_t)gy * W + gx) * 8 + (co & 7)) = o;
+			}
+		}
+		else if constexpr (EPI == LP_EPI_MASK)
+		{
+#pragma unroll
+			for (int r = 0; r < 4; r++)
+			{
+				const int gy = ty0 + wave * 4 + r;
+				if (gy >= H) continue;
+				const size_t at = (((size_t)img * (Cout >> 3) + (co >> 3)) * plane + (size_t)gy * W + gx) * 8 + (co & 7);
+				*(float4 *)(out + at) = lp_mask(*(const float4 *)(act + at), make_float4(tot[mt][r][0], tot[mt][r][1], tot[mt][r][2], tot[mt][r][3]));
+			}
+		}
+		else
+		{
+			const size_t cbase = ((size_t)img * (Cout >> 3) + (co >> 3)) * ((size_t)Ht * Wt) * 8 + (co & 7);
+			// the tap's own gradient, masked, at a position no window covers -- or with `v` added, at a position of a window
+			auto put = [&](int y, int x, const float4 v) {
+				const size_t at = cbase + ((size_t)y * Wt + x) * 8;
+				const float4 t = *(const float4 *)(tapgrad + at);
+				*(float4 *)(out + at) = lp_mask(*(const float4 *)(act + at), make_float4(v.x + t.x, v.y + t.y, v.z + t.z, v.w + t.w));
+			};
+			const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+			const bool edge_c = (Wt & 1) && gx == W - 1;
+#pragma unroll
+			for (int r = 0; r < 4; r++)
+			{
+				const int gy = ty0 + wave * 4 + r;
+				if (gy >= H) continue;
+				float a[4][4]; // [window position 2 j + i][channel]
+#pragma unroll
+				for (int p = 0; p < 4; p++)
+				{
+					const float4 v = *(const float4 *)(act + cbase + ((size_t)(2 * gy + (p >> 1)) * Wt + 2 * gx + (p & 1)) * 8);
+					a[p][0] = v.x; a[p][1] = v.y; a[p][2] = v.z; a[p][3] = v.w;
+				}
+				int first[4];
+#pragma unroll
+				for (int q = 0; q < 4; q++)
+				{
+					float best = a[0][q];
+					first[q] = 0;
+#pragma unroll
+					for (int p = 1; p < 4; p++)
+						if (a[p][q] > best) { best = a[p][q]; first[q] = p; }
+				}
+#pragma unroll
+				for (int p = 0; p < 4; p++)
+					put(2 * gy + (p >> 1), 2 * gx + (p & 1), make_float4(first[0] == p ? tot[mt][r][0] : 0.0f, first[1] == p ? tot[mt][r][1] : 0.0f,
+						first[2] == p ? tot[mt][r][2] : 0.0f, first[3] == p ? tot[mt][r][3] : 0.0f));
+				const bool edge_r = (Ht & 1) && gy == H - 1;
+				if (edge_r) { put(Ht - 1, 2 * gx, zero); put(Ht - 1, 2 * gx + 1, zero); }
+				if (edge_c) { put(2 * gy, Wt - 1, zero); put(2 * gy + 1, Wt - 1, zero); }
+				if (edge_r && edge_c) put(Ht - 1, Wt - 1, zero);
+			}
 		}
 	}
 }
 
 // ---- head: norms, weighted squared difference, sum; 2x2 max pool of both maps ----------------------------------------------
-// feat: [2 N][C / 8][H][W][8], x's pictures then y's. A wave owns 2 rows x 8 pixels (four pool windows); lane = half + 2 xx + 16 r +
+// featx, featy: [N][C / 8][H][W][8], the tap of x's and of y's pictures. A wave owns 2 rows x 8 pixels (four pool windows); lane = half + 2 xx + 16 r +
 // 32 par holds the channels 4 half .. 4 half + 3 of the blocks par, par + 2, ... of pixel (2 qy + r, x0 + xx): 8 pixels x 32 bytes of
-// a row and block are one 256-byte run. pooled (optional): [2 N][C / 8][H / 2][W / 2][8]. features (optional): x's tap, [N,C,H,W].
-// partials[n * gridDim.y * gridDim.x + block] = the sum of d over the block's pixels, waves added in wave order.
-__global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, const float *__restrict__ feat, const float *__restrict__ lin,
-	float *__restrict__ pooled, float *__restrict__ features, double *__restrict__ partials)
+// a row and block are one 256-byte run. pooledx, pooledy (optional, both or none): [N][C / 8][H / 2][W / 2][8]. features (optional):
+// x's tap, [N,C,H,W]. partials[n * gridDim.y * gridDim.x + block] = the sum of d over the block's pixels, waves added in wave order.
+// KEEP (the differentiable forward) adds a second pass over the channels that writes tapgrad, in featx's layout: the gradient of the
+// tap's value with respect to x's tap map, masked by the ReLU rule. With s = sqrt(sum a^2), n = s + 1e-10, u_c = w_c (a_c / nx -
+// b_c / ny):   d value / d a_c = (2 u_c / nx - 2 a_c (sum_j u_j a_j) / (nx^2 s)) / (H W),   sum_j u_j a_j = wxx / nx - wxy / ny
+// from the sums of the first pass. Everything is formed in double from the float inputs; equal pictures give a_c / nx - b_c / ny = 0
+// and wxx / nx - wxy / ny = 0 exactly, so every element is exactly 0. At s = 0 (a tap vector that is all zero) the second term is
+// taken as 0, its limit -- the reference's sqrt backward yields inf * 0 = NaN there -- and the mask drops the first.
+template <bool KEEP>
+__global__ void __launch_bounds__(256) k_lpips_head(int C, int H, int W, const float *__restrict__ featx, const float *__restrict__ featy,
+	const float *__restrict__ lin, float *__restrict__ pooledx, float *__restrict__ pooledy, float *__restrict__ features, double *__restrict__ partials,
+	float *__restrict__ tapgrad)
 {
 	__shared__ double s_w[4];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -238,7 +360,7 @@ __global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, 
 	const int gy = 2 * blockIdx.y + r, gx = blockIdx.x * LP_HEAD_W + wave * 8 + xx;
 	const bool in = gy < H && gx < W;
 	const int Hp = H >> 1, Wp = W >> 1;
-	const bool pool_out = pooled != nullptr && r == 0 && (xx & 1) == 0 && (int)blockIdx.y < Hp && (gx >> 1) < Wp;
+	const bool pool_out = pooledx != nullptr && r == 0 && (xx & 1) == 0 && (int)blockIdx.y < Hp && (gx >> 1) < Wp;
 	const size_t plane = (size_t)H * W, pplane = (size_t)Hp * Wp;
 	const size_t pix = (size_t)gy * W + gx, ppix = (size_t)blockIdx.y * Wp + (gx >> 1);
 	double sxx = 0.0, syy = 0.0, wxx = 0.0, wyy = 0.0, wxy = 0.0;
@@ -247,8 +369,8 @@ __global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, 
 		float4 ax = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ay = ax;
 		if (in)
 		{
-			ax = *(const float4 *)(feat + (((size_t)n * CB + cb) * plane + pix) * 8 + 4 * half);
-			ay = *(const float4 *)(feat + (((size_t)(N + n) * CB + cb) * plane + pix) * 8 + 4 * half);
+			ax = *(const float4 *)(featx + (((size_t)n * CB + cb) * plane + pix) * 8 + 4 * half);
+			ay = *(const float4 *)(featy + (((size_t)n * CB + cb) * plane + pix) * 8 + 4 * half);
 		}
 		const float4 wv = *(const float4 *)(lin + cb * 8 + 4 * half);
 		const float xa[4] = { ax.x, ax.y, ax.z, ax.w }, ya[4] = { ay.x, ay.y, ay.z, ay.w }, wa[4] = { wv.x, wv.y, wv.z, wv.w };
@@ -264,7 +386,7 @@ __global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, 
 			float *F = features + ((size_t)n * C + cb * 8 + 4 * half) * plane + pix;
 			F[0] = ax.x; F[plane] = ax.y; F[2 * plane] = ax.z; F[3 * plane] = ax.w;
 		}
-		if (pooled != nullptr) // uniform: every lane takes part in the exchanges
+		if (pooledx != nullptr) // uniform: every lane takes part in the exchanges
 		{
 			float mx[4], my[4];
 #pragma unroll
@@ -275,8 +397,8 @@ __global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, 
 			}
 			if (pool_out)
 			{
-				*(float4 *)(pooled + (((size_t)n * CB + cb) * pplane + ppix) * 8 + 4 * half) = make_float4(mx[0], mx[1], mx[2], mx[3]);
-				*(float4 *)(pooled + (((size_t)(N + n) * CB + cb) * pplane + ppix) * 8 + 4 * half) = make_float4(my[0], my[1], my[2], my[3]);
+				*(float4 *)(pooledx + (((size_t)n * CB + cb) * pplane + ppix) * 8 + 4 * half) = make_float4(mx[0], mx[1], mx[2], mx[3]);
+				*(float4 *)(pooledy + (((size_t)n * CB + cb) * pplane + ppix) * 8 + 4 * half) = make_float4(my[0], my[1], my[2], my[3]);
 			}
 		}
 	}
@@ -286,12 +408,89 @@ __global__ void __launch_bounds__(256) k_lpips_head(int N, int C, int H, int W, 
 	const double nx = sqrt(sxx) + 1e-10, ny = sqrt(syy) + 1e-10;
 	const double q1 = wxx / (nx * nx), q2 = wxy / (nx * ny), q3 = wyy / (ny * ny);
 	double d = in ? (q1 - 2.0 * q2) + q3 : 0.0; // equal pictures: q - 2 q + q = 0 exactly
+	if constexpr (KEEP)
+	{
+		if (in) // every lane of a pixel holds the pixel's sums
+		{
+			const double sx = sqrt(sxx), rnx = 1.0 / nx, rny = 1.0 / ny, rhw = 1.0 / ((double)H * (double)W);
+			const double ua = wxx * rnx - wxy * rny;
+			const double k2 = sx > 0.0 ? ua * rnx * rnx / sx : 0.0;
+			for (int cb = par; cb < CB; cb += 2)
+			{
+				const size_t at = (((size_t)n * CB + cb) * plane + pix) * 8 + 4 * half;
+				const float4 ax = *(const float4 *)(featx + at), ay = *(const float4 *)(featy + at), wv = *(const float4 *)(lin + cb * 8 + 4 * half);
+				const float xa[4] = { ax.x, ax.y, ax.z, ax.w }, ya[4] = { ay.x, ay.y, ay.z, ay.w }, wa[4] = { wv.x, wv.y, wv.z, wv.w };
+				float g[4];
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+				{
+					const double a = (double)xa[j], u = (double)wa[j] * (a * rnx - (double)ya[j] * rny);
+					g[j] = xa[j] > 0.0f ? (float)((2.0 * u * rnx - 2.0 * a * k2) * rhw) : 0.0f;
+				}
+				*(float4 *)(tapgrad + at) = make_float4(g[0], g[1], g[2], g[3]);
+			}
+		}
+	}
 	// the wave's 16 pixels (every lane of a pixel holds the same d)
 	d += __shfl_xor(d, 2); d += __shfl_xor(d, 4); d += __shfl_xor(d, 8); d += __shfl_xor(d, 16);
 	if (lane == 0) s_w[wave] = d;
 	__syncthreads();
 	if (threadIdx.x == 0)
 		partials[((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// ---- backward of the first layer: 64 -> 3, the z-score's 1 / std and the upstream gradient ---------------------------------
+// dact: [N][8][H][W][8], the gradient at relu1_1 (already masked). A workgroup owns 16 x 16 pixels, a thread one pixel and its three
+// channels; per 8-channel chunk the 18 x 18 halo tile goes through LDS, so the map is read once. wb: [chunk][tap][8][3], the flipped
+// taps (fr_lpips_pack_backward_weights). Two levels as in k_lpips_conv: a chunk's 72 products per channel are one fmaf chain from
+// zero, the eight chunk sums are added in chunk order. upstream[0] is read on the device. dx: [N,3,H,W] planes.
+__global__ void __launch_bounds__(256) k_lpips_conv0_bwd(int H, int W, const float *__restrict__ dact, const float *__restrict__ wb,
+	const float *__restrict__ upstream, float *__restrict__ dx)
+{
+	__shared__ __attribute__((aligned(16))) float sw[8 * 9 * 8 * 3];
+	__shared__ __attribute__((aligned(16))) float il[2 * LP_NPIX * 4];
+	const int n = blockIdx.z, tx0 = blockIdx.x * LP_TILE, ty0 = blockIdx.y * LP_TILE;
+	const int px = threadIdx.x & 15, py = threadIdx.x >> 4;
+	const size_t plane = (size_t)H * W;
+	for (int i = threadIdx.x; i < 8 * 9 * 8 * 3; i += 256) sw[i] = wb[i];
+	float tot[3] = { 0.0f, 0.0f, 0.0f };
+	for (int ck = 0; ck < 8; ck++)
+	{
+		__syncthreads(); // the previous chunk's reads are done (and, the first time, sw is written)
+		const float *base = dact + ((size_t)n * 8 + ck) * plane * 8;
+		for (int i = threadIdx.x; i < 2 * LP_NPIX; i += 256)
+		{
+			const int pix = i >> 1, cg = i & 1;
+			const int hy = pix / LP_HALO, hx = pix - hy * LP_HALO;
+			const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
+			float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+			if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *(const float4 *)(base + ((size_t)gy * W + gx) * 8 + 4 * cg);
+			((float4 *)il)[cg * LP_NPIX + pix] = v;
+		}
+		__syncthreads();
+		float acc[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+		for (int t = 0; t < 9; t++)
+#pragma unroll
+			for (int cg = 0; cg < 2; cg++)
+			{
+				const float4 v = ((const float4 *)il)[cg * LP_NPIX + (py + t / 3) * LP_HALO + px + t % 3];
+				const float va[4] = { v.x, v.y, v.z, v.w };
+				const float *w = sw + ((ck * 9 + t) * 8 + 4 * cg) * 3;
+#pragma unroll
+				for (int c = 0; c < 4; c++)
+#pragma unroll
+					for (int ci = 0; ci < 3; ci++) acc[ci] = fmaf(va[c], w[c * 3 + ci], acc[ci]);
+			}
+#pragma unroll
+		for (int ci = 0; ci < 3; ci++) tot[ci] += acc[ci];
+	}
+	const int gy = ty0 + py, gx = tx0 + px;
+	if (gy >= H || gx >= W) return;
+	const float sd[3] = { .458f, .448f, .450f };
+	const float up = upstream[0];
+#pragma unroll
+	for (int ci = 0; ci < 3; ci++) dx[((size_t)n * 3 + ci) * plane + (size_t)gy * W + gx] = tot[ci] / sd[ci] * up;
 }
 
 // one workgroup: value = (sum of the partials, in double, a fixed order) / (H W) -- the tap's mean summed over the batch.
@@ -411,20 +610,209 @@ extern "C" int fr_lpips_forward(const fr_lpips_args *a)
 	for (int l = 1; l < LP_LAYERS; l++)
 	{
 		const dim3 grid((W + LP_TILE - 1) / LP_TILE, (H + LP_TILE - 1) / LP_TILE, NI * (lp_cout[l] / 64));
-		hipLaunchKernelGGL(k_lpips_conv, grid, dim3(256), 0, stream, H, W, lp_cin[l], lp_cout[l], buf[cur], pk + P.w[l], pk + P.b[l], buf[cur ^ 1]);
+		hipLaunchKernelGGL(k_lpips_conv<LP_EPI_RELU>, grid, dim3(256), 0, stream, H, W, lp_cin[l], lp_cout[l], (const float *)buf[cur], pk + P.w[l], pk + P.b[l],
+			buf[cur ^ 1], (const float *)nullptr, (const float *)nullptr, 0, 0);
 		if ((rc = check_launch("lpips_forward (convolution)", stream, debug)) != FR_OK) return rc;
 		mark();
 		cur ^= 1;
 		if (l != lp_tap_layer[tap]) continue;
 		const bool last = tap == LP_TAPS - 1;
 		const dim3 hgrid((W + LP_HEAD_W - 1) / LP_HEAD_W, (H + 1) / 2, N);
-		hipLaunchKernelGGL(k_lpips_head, hgrid, dim3(256), 0, stream, N, lp_tap_c[tap], H, W, buf[cur], pk + P.lin[tap], last ? nullptr : buf[cur ^ 1],
-			a->out_features[tap], partials);
+		const size_t ys = (size_t)N * lp_tap_c[tap] * H * W, yp = (size_t)N * lp_tap_c[tap] * (H >> 1) * (W >> 1); // y's pictures follow x's
+		hipLaunchKernelGGL(k_lpips_head<false>, hgrid, dim3(256), 0, stream, lp_tap_c[tap], H, W, (const float *)buf[cur], (const float *)buf[cur] + ys,
+			pk + P.lin[tap], last ? nullptr : buf[cur ^ 1], last ? nullptr : buf[cur ^ 1] + yp, a->out_features[tap], partials, (float *)nullptr);
 		hipLaunchKernelGGL(k_lpips_finish, dim3(1), dim3(1024), 0, stream, (long long)N * hgrid.x * hgrid.y, (double)H * (double)W, tap, partials, scal,
 			a->out_taps, a->out);
 		if ((rc = check_launch("lpips_forward (head)", stream, debug)) != FR_OK) return rc;
 		mark();
 		cur ^= 1; H >>= 1; W >>= 1; tap++;
 	}
+	return FR_OK;
+}
+
+// ---- the differentiable path: backward weights, the forward that keeps x's maps, the backward pass -----------------------------
+
+extern "C" size_t fr_lpips_backward_packed_bytes(void)
+{
+	return lp_back_packed().floats * sizeof(float);
+}
+
+extern "C" int fr_lpips_pack_backward_weights(const float *const *conv_weights, void *packed_backward)
+{
+	if (!conv_weights) { set_error("lpips_pack_backward_weights: conv_weights is null"); return FR_ERR_INVALID; }
+	if (!packed_backward) { set_error("lpips_pack_backward_weights: packed_backward is null"); return FR_ERR_INVALID; }
+	for (int l = 0; l < LP_LAYERS; l++)
+		if (!conv_weights[l]) { set_error("lpips_pack_backward_weights: conv_weights[%d] is null", l); return FR_ERR_INVALID; }
+	const LpBackPacked P = lp_back_packed();
+	float *out = (float *)packed_backward;
+	// first layer: [chunk of 8 outputs][tap][8][3 inputs], the taps flipped (tap t reads W[.][.][8 - t])
+	for (int co = 0; co < 64; co++)
+		for (int ci = 0; ci < 3; ci++)
+			for (int t = 0; t < 9; t++) out[P.w[0] + (((size_t)(co >> 3) * 9 + t) * 8 + (co & 7)) * 3 + ci] = conv_weights[0][(co * 3 + ci) * 9 + 8 - t];
+	// W'[ci][co][t] = W[co][ci][8 - t] in k_lpips_conv's slabs: the backward convolution's outputs are the forward's inputs
+	for (int l = 1; l < LP_LAYERS; l++)
+	{
+		const int ci_n = lp_cin[l], co_n = lp_cout[l], kb = co_n / 8; // kb: 8-channel chunks of the backward's K
+		const float *w = conv_weights[l];
+		float *o = out + P.w[l];
+		for (int co = 0; co < co_n; co++)
+			for (int ci = 0; ci < ci_n; ci++)
+				for (int t = 0; t < 9; t++)
+				{
+					const size_t slab = (size_t)(ci / 64) * kb + co / 8;
+					const int cg = (co & 7) >> 2, hh = co & 3;
+					o[slab * LP_SLAB + ((size_t)(t * 2 + cg) * 64 + (ci & 63)) * 4 + hh] = w[((size_t)co * ci_n + ci) * 9 + 8 - t];
+				}
+	}
+	return FR_OK;
+}
+
+extern "C" int64_t fr_lpips_keep_workspace_bytes(int32_t N, int32_t H, int32_t W)
+{
+	if (!lp_sizes_ok(N, H, W))
+	{
+		set_error("lpips_keep_workspace_bytes: bad sizes N=%d H=%d W=%d (N 1 .. %d, H and W 16 .. %d)", N, H, W, LP_MAX_N, LP_MAX_HW);
+		return -1;
+	}
+	return (int64_t)lp_keep(N, H, W).bytes;
+}
+
+extern "C" int64_t fr_lpips_keep_activation_offset(int32_t N, int32_t H, int32_t W, int32_t layer)
+{
+	if (!lp_sizes_ok(N, H, W))
+	{
+		set_error("lpips_keep_activation_offset: bad sizes N=%d H=%d W=%d (N 1 .. %d, H and W 16 .. %d)", N, H, W, LP_MAX_N, LP_MAX_HW);
+		return -1;
+	}
+	if (layer < 0 || layer >= LP_LAYERS) { set_error("lpips_keep_activation_offset: layer=%d is outside 0 .. %d", layer, LP_LAYERS - 1); return -1; }
+	return (int64_t)lp_keep(N, H, W).act[layer];
+}
+
+// the checks the forward, the keeping forward and the backward share; `who` names the call
+static int lp_check_sizes(const char *who, uint32_t size, size_t want, const char *strct, int N, int H, int W)
+{
+	if (size < want) { set_error("%s: size=%u is smaller than %s (%zu)", who, size, strct, want); return FR_ERR_INVALID; }
+	if (N < 1 || N > LP_MAX_N) { set_error("%s: N=%d is outside 1 .. %d", who, N, LP_MAX_N); return FR_ERR_INVALID; }
+	if (H < 16 || H > LP_MAX_HW) { set_error("%s: H=%d is outside 16 .. %d (the fourth pool needs 16 rows)", who, H, LP_MAX_HW); return FR_ERR_INVALID; }
+	if (W < 16 || W > LP_MAX_HW) { set_error("%s: W=%d is outside 16 .. %d (the fourth pool needs 16 columns)", who, W, LP_MAX_HW); return FR_ERR_INVALID; }
+	return FR_OK;
+}
+
+extern "C" int fr_lpips_forward_keep(const fr_lpips_keep_args *a)
+{
+	int rc;
+	if (!a) { set_error("lpips_forward_keep: args is null"); return FR_ERR_INVALID; }
+	if ((rc = lp_check_sizes("lpips_forward_keep", a->size, sizeof(fr_lpips_keep_args), "fr_lpips_keep_args", a->N, a->H, a->W)) != FR_OK) return rc;
+	if (!a->x) { set_error("lpips_forward_keep: x is null"); return FR_ERR_INVALID; }
+	if (!a->y) { set_error("lpips_forward_keep: y is null"); return FR_ERR_INVALID; }
+	if (!a->packed) { set_error("lpips_forward_keep: packed is null"); return FR_ERR_INVALID; }
+	if (!a->workspace) { set_error("lpips_forward_keep: workspace is null"); return FR_ERR_INVALID; }
+	if (!a->keep) { set_error("lpips_forward_keep: keep is null"); return FR_ERR_INVALID; }
+	if (!a->out) { set_error("lpips_forward_keep: out is null"); return FR_ERR_INVALID; }
+	if (((uintptr_t)a->packed & 15) || ((uintptr_t)a->workspace & 255) || ((uintptr_t)a->keep & 255))
+	{
+		set_error("lpips_forward_keep: packed must be 16-byte, workspace and keep 256-byte aligned");
+		return FR_ERR_INVALID;
+	}
+	const int N = a->N;
+	const bool debug = a->debug != 0;
+	hipStream_t stream = (hipStream_t)a->stream;
+	const LpPacked P = lp_packed();
+	const LpWorkspace L = lp_workspace(N, a->H, a->W);
+	const LpKeep K = lp_keep(N, a->H, a->W);
+	const float *pk = (const float *)a->packed;
+	char *ws = (char *)a->workspace, *kp = (char *)a->keep;
+	double *scal = (double *)(ws + L.scal), *partials = (double *)(ws + L.partials);
+	// y's pictures ping-pong in the first half of the two buffers; the second half takes x's pooled tap, the next group's input
+	float *buf[2] = { (float *)(ws + L.buf[0]), (float *)(ws + L.buf[1]) };
+	const size_t half = L.buf_floats / 2;
+	int H = a->H, W = a->W, cur = 0, stage = 0;
+	auto mark = [&]() { if (a->stage_events && a->stage_events[stage]) (void)hipEventRecord((hipEvent_t)a->stage_events[stage], stream); stage++; };
+	mark();
+	{
+		const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), 8, N);
+		hipLaunchKernelGGL(k_lpips_conv0, grid, dim3(256), 0, stream, H, W, a->x, 0, pk + P.w[0], pk + P.b[0], (float *)(kp + K.act[0]));
+		hipLaunchKernelGGL(k_lpips_conv0, grid, dim3(256), 0, stream, H, W, a->y, 0, pk + P.w[0], pk + P.b[0], buf[0]);
+		if ((rc = check_launch("lpips_forward_keep (first layer)", stream, debug)) != FR_OK) return rc;
+		mark();
+	}
+	const float *xin = (const float *)(kp + K.act[0]);
+	int tap = 0;
+	for (int l = 1; l < LP_LAYERS; l++)
+	{
+		const dim3 grid((W + LP_TILE - 1) / LP_TILE, (H + LP_TILE - 1) / LP_TILE, N * (lp_cout[l] / 64));
+		float *xout = (float *)(kp + K.act[l]);
+		hipLaunchKernelGGL(k_lpips_conv<LP_EPI_RELU>, grid, dim3(256), 0, stream, H, W, lp_cin[l], lp_cout[l], xin, pk + P.w[l], pk + P.b[l], xout,
+			(const float *)nullptr, (const float *)nullptr, 0, 0);
+		hipLaunchKernelGGL(k_lpips_conv<LP_EPI_RELU>, grid, dim3(256), 0, stream, H, W, lp_cin[l], lp_cout[l], (const float *)buf[cur], pk + P.w[l], pk + P.b[l],
+			buf[cur ^ 1], (const float *)nullptr, (const float *)nullptr, 0, 0);
+		if ((rc = check_launch("lpips_forward_keep (convolution)", stream, debug)) != FR_OK) return rc;
+		mark();
+		cur ^= 1; xin = xout;
+		if (l != lp_tap_layer[tap]) continue;
+		const bool last = tap == LP_TAPS - 1;
+		const dim3 hgrid((W + LP_HEAD_W - 1) / LP_HEAD_W, (H + 1) / 2, N);
+		hipLaunchKernelGGL(k_lpips_head<true>, hgrid, dim3(256), 0, stream, lp_tap_c[tap], H, W, xin, (const float *)buf[cur], pk + P.lin[tap],
+			last ? nullptr : buf[cur ^ 1] + half, last ? nullptr : buf[cur ^ 1], (float *)nullptr, partials, (float *)(kp + K.tg[tap]));
+		hipLaunchKernelGGL(k_lpips_finish, dim3(1), dim3(1024), 0, stream, (long long)N * hgrid.x * hgrid.y, (double)H * (double)W, tap, partials, scal,
+			a->out_taps, a->out);
+		if ((rc = check_launch("lpips_forward_keep (head)", stream, debug)) != FR_OK) return rc;
+		mark();
+		cur ^= 1; xin = buf[cur] + half; H >>= 1; W >>= 1; tap++;
+	}
+	return FR_OK;
+}
+
+extern "C" int fr_lpips_backward(const fr_lpips_backward_args *a)
+{
+	int rc;
+	if (!a) { set_error("lpips_backward: args is null"); return FR_ERR_INVALID; }
+	if ((rc = lp_check_sizes("lpips_backward", a->size, sizeof(fr_lpips_backward_args), "fr_lpips_backward_args", a->N, a->H, a->W)) != FR_OK) return rc;
+	if (!a->packed_backward) { set_error("lpips_backward: packed_backward is null"); return FR_ERR_INVALID; }
+	if (!a->keep) { set_error("lpips_backward: keep is null"); return FR_ERR_INVALID; }
+	if (!a->workspace) { set_error("lpips_backward: workspace is null"); return FR_ERR_INVALID; }
+	if (!a->grad_out) { set_error("lpips_backward: grad_out is null"); return FR_ERR_INVALID; }
+	if (!a->grad_x) { set_error("lpips_backward: grad_x is null"); return FR_ERR_INVALID; }
+	if (((uintptr_t)a->packed_backward & 15) || ((uintptr_t)a->workspace & 255) || ((uintptr_t)a->keep & 255))
+	{
+		set_error("lpips_backward: packed_backward must be 16-byte, workspace and keep 256-byte aligned");
+		return FR_ERR_INVALID;
+	}
+	const int N = a->N;
+	const bool debug = a->debug != 0;
+	hipStream_t stream = (hipStream_t)a->stream;
+	const LpBackPacked P = lp_back_packed();
+	const LpWorkspace L = lp_workspace(N, a->H, a->W);
+	const LpKeep K = lp_keep(N, a->H, a->W);
+	const float *pb = (const float *)a->packed_backward;
+	const char *kp = (const char *)a->keep;
+	char *ws = (char *)a->workspace;
+	float *buf[2] = { (float *)(ws + L.buf[0]), (float *)(ws + L.buf[1]) }; // the gradient at a layer's output ping-pongs
+	int cur = 0, stage = 0, tap = LP_TAPS - 1;
+	auto mark = [&]() { if (a->stage_events && a->stage_events[stage]) (void)hipEventRecord((hipEvent_t)a->stage_events[stage], stream); stage++; };
+	mark();
+	const float *din = (const float *)(kp + K.tg[tap]); // the chain starts at relu5_3: the last tap's gradient, masked by the head
+	for (int l = LP_LAYERS - 1; l >= 1; l--)
+	{
+		const int H = a->H >> lp_layer_shift(l), W = a->W >> lp_layer_shift(l);
+		const dim3 grid((W + LP_TILE - 1) / LP_TILE, (H + LP_TILE - 1) / LP_TILE, N * (lp_cin[l] / 64));
+		const float *act = (const float *)(kp + K.act[l - 1]);
+		if (lp_layer_shift(l) != lp_layer_shift(l - 1)) // a pool in front of layer l: its input is the pooled tap
+		{
+			tap--;
+			hipLaunchKernelGGL(k_lpips_conv<LP_EPI_POOL_TAP>, grid, dim3(256), 0, stream, H, W, lp_cout[l], lp_cin[l], din, pb + P.w[l], (const float *)nullptr,
+				buf[cur], act, (const float *)(kp + K.tg[tap]), a->H >> lp_layer_shift(l - 1), a->W >> lp_layer_shift(l - 1));
+		}
+		else
+			hipLaunchKernelGGL(k_lpips_conv<LP_EPI_MASK>, grid, dim3(256), 0, stream, H, W, lp_cout[l], lp_cin[l], din, pb + P.w[l], (const float *)nullptr,
+				buf[cur], act, (const float *)nullptr, 0, 0);
+		if ((rc = check_launch("lpips_backward (convolution)", stream, debug)) != FR_OK) return rc;
+		mark();
+		din = buf[cur]; cur ^= 1;
+	}
+	const dim3 grid((a->W + LP_TILE - 1) / LP_TILE, (a->H + LP_TILE - 1) / LP_TILE, N);
+	hipLaunchKernelGGL(k_lpips_conv0_bwd, grid, dim3(256), 0, stream, a->H, a->W, din, pb + P.w[0], a->grad_out, a->grad_x);
+	if ((rc = check_launch("lpips_backward (first layer)", stream, debug)) != FR_OK) return rc;
+	mark();
 	return FR_OK;
 }

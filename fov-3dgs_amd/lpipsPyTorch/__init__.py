@@ -16,17 +16,29 @@ Semantics are the reference's (modules/networks.py:41-64, :89-96; modules/utils.
 applied to the picture as handed in ([0, 1] pictures are not rescaled to [-1, 1]), and the result is ONE ``[1,1,1,1]`` value, the
 sum over the five taps AND over the batch -- ``torch.sum(torch.cat(res, 0), 0, True)``; the scripts pass N = 1.
 
-Only 'vgg' is built. This is the evaluation metric: there is no backward pass, and an input that requires grad is refused. GPU
-tensors only, there is no CPU fallback. The weights are packed once per object and device, the workspace (two activation buffers
-of 2 N x 64 x H x W floats, 2.1 GB for one 1080 x 1920 pair) is kept per picture size; use an object from one stream at a time."""
+Only 'vgg' is built. ``lpips`` and ``LPIPS`` are the evaluation metric: they build no backward pass and refuse an input that
+requires grad. GPU tensors only, there is no CPU fallback. The weights are packed once per object and device, the workspace (two
+activation buffers of 2 N x 64 x H x W floats, 2.1 GB for one 1080 x 1920 pair) is kept per picture size; use an object from one
+stream at a time.
+
+The training loss is a pair of names of its own, ``lpips_loss(x, y, net_type='vgg', version='0.1', weights=None)`` and
+``LPIPSLoss(net_type='vgg', version='0.1', weights=None)``: the same value, bit for bit, and when ``x`` requires grad a
+``grad_fn`` whose backward pass is HIP as well (fr_lpips_forward_keep, fr_lpips_backward). ``y`` is the target and must not
+require grad. A differentiable call keeps x's 13 post-ReLU maps and the five tap gradients in a buffer of its own, held by its
+autograd node (3.25 GB for one 1080 x 1920 pair) and freed by ``backward()``; calls and their backward passes may interleave in
+any order. The gradient follows torch's rules -- a ReLU passes it where the kept output is > 0, a 2 x 2 max pool sends it to the
+first maximum of its window in row-major order -- with ONE stated deviation: at a pixel whose tap vector is entirely zero the
+reference's ``sqrt`` backward yields inf * 0 = NaN and poisons the whole gradient; here the term a_c (sum_j u_j a_j) / (n^2 s)
+is taken as 0 at s = 0, its limit, the ReLU rule zeroes the rest, and the gradient stays finite."""
 import ctypes as C
 import collections.abc
+import weakref
 
 import torch
 
 from .. import _native
 
-__all__ = ["lpips", "LPIPS", "set_default_weights", "load_weights", "pack_weights"]
+__all__ = ["lpips", "LPIPS", "lpips_loss", "LPIPSLoss", "set_default_weights", "load_weights", "pack_weights", "pack_backward_weights"]
 
 CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)  # the convolutions of vgg16().features
 CONV_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
@@ -38,9 +50,14 @@ MIN_SIZE = 16  # below it the fourth pool has no output (the reference raises th
 STAGES = ("conv1_1", "conv1_2", "head1", "conv2_1", "conv2_2", "head2", "conv3_1", "conv3_2", "conv3_3", "head3", "conv4_1", "conv4_2",
           "conv4_3", "head4", "conv5_1", "conv5_2", "conv5_3", "head5")
 
+# the 13 stages between the 14 handles of fr_lpips_backward_args.stage_events
+BACKWARD_STAGES = ("conv5_3", "conv5_2", "conv5_1", "conv4_3", "conv4_2", "conv4_1", "conv3_3", "conv3_2", "conv3_1", "conv2_2", "conv2_1",
+                   "conv1_2", "conv1_1")
+
 PACK_COUNT = 0  # how often pack_weights has run (the tests check that a loop over views packs once)
 _default_weights = None
 _cache = {}  # id(weights object) -> (weights object, LPIPS): the functional form packs once per weights object and device
+_loss_cache = {}  # the same for lpips_loss and LPIPSLoss
 
 
 def _get(mapping, names, what):
@@ -94,6 +111,17 @@ def pack_weights(weights):
     if rc != 0:
         raise RuntimeError(f"fovraster lpips_pack_weights failed ({rc}): {_native.last_error()}")
     PACK_COUNT += 1
+    return packed
+
+
+def pack_backward_weights(weights):
+    """weights -> the backward pass's weights (the transposed, flipped slabs), a CPU uint8 tensor of fr_lpips_backward_packed_bytes"""
+    ws, _, _ = _normalise(weights)
+    lib = _native.load()
+    packed = torch.empty(lib.fr_lpips_backward_packed_bytes(), dtype=torch.uint8)
+    rc = lib.fr_lpips_pack_backward_weights((C.c_void_p * len(ws))(*[t.data_ptr() for t in ws]), packed.data_ptr())
+    if rc != 0:
+        raise RuntimeError(f"fovraster lpips_pack_backward_weights failed ({rc}): {_native.last_error()}")
     return packed
 
 
@@ -169,13 +197,8 @@ class LPIPS(torch.nn.Module):
         if not x.is_cuda or x.device != y.device:
             raise RuntimeError(f"fovraster LPIPS needs x and y on one GPU (got {x.device} and {y.device}): there is no CPU fallback")
 
-    def _run(self, x, y, want_taps=False, want_features=False, stage_events=None):
-        self._check(x, y)
+    def _workspace(self, dev, N, H, W):
         lib = _native.load()
-        x, y = x.detach().contiguous(), y.detach().contiguous()
-        dev = x.device
-        N, _, H, W = x.shape
-        packed = self._packed_on(dev)
         key, work = self._work.get(dev, (None, None))
         if key != (N, H, W):
             nbytes = lib.fr_lpips_workspace_bytes(N, H, W)
@@ -184,6 +207,16 @@ class LPIPS(torch.nn.Module):
             self._work.pop(dev, None)
             work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._work[dev] = ((N, H, W), work)
+        return work
+
+    def _run(self, x, y, want_taps=False, want_features=False, stage_events=None):
+        self._check(x, y)
+        lib = _native.load()
+        x, y = x.detach().contiguous(), y.detach().contiguous()
+        dev = x.device
+        N, _, H, W = x.shape
+        packed = self._packed_on(dev)
+        work = self._workspace(dev, N, H, W)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         taps = torch.empty(5, dtype=torch.float32, device=dev) if want_taps else None
         feats = [torch.empty((N, c, H >> k, W >> k), dtype=torch.float32, device=dev) for k, c in enumerate(TAP_CHANNELS)] if want_features else None
@@ -228,6 +261,142 @@ class LPIPS(torch.nn.Module):
     def features(self, x):
         """the five tap maps of x before the normalisation, [N,C_k,H >> k,W >> k]"""
         return self._run(x, x, want_features=True)[2]
+
+
+def _events(lib, n):
+    return (C.c_void_p * n)(*[lib.fr_event_create() for _ in range(n)])
+
+
+def _elapsed(lib, ev, names):
+    out, ms = {}, C.c_float()
+    for i, name in enumerate(names):
+        if lib.fr_event_elapsed_ms(ev[i], ev[i + 1], C.byref(ms)) != 0:
+            raise RuntimeError(f"fovraster: {_native.last_error()}")
+        out[name] = ms.value
+    return out
+
+
+class _LPIPSFunction(torch.autograd.Function):
+    """value = LPIPS(x, y), differentiable in x. The kept state is saved with the node: it belongs to this call alone."""
+
+    @staticmethod
+    def forward(ctx, x, y, crit):
+        lib = _native.load()
+        xc, yc = x.detach().contiguous(), y.detach().contiguous()
+        dev = xc.device
+        N, _, H, W = xc.shape
+        nbytes = lib.fr_lpips_keep_workspace_bytes(N, H, W)
+        if nbytes < 0:
+            raise ValueError(f"lpipsPyTorch: {_native.last_error()}")
+        keep = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        a = _native.LpipsKeepArgs(size=C.sizeof(_native.LpipsKeepArgs), N=N, H=H, W=W, debug=0, x=xc.data_ptr(), y=yc.data_ptr(),
+                                  packed=crit._packed_on(dev).data_ptr(), workspace=crit._workspace(dev, N, H, W).data_ptr(),
+                                  keep=keep.data_ptr(), out=out.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        if crit._forward_events is not None:
+            a.stage_events = crit._forward_events
+        with torch.cuda.device(dev):
+            rc = lib.fr_lpips_forward_keep(C.byref(a))
+        if rc != 0:
+            raise RuntimeError(f"fovraster lpips_forward_keep failed ({rc}): {_native.last_error()}")
+        ctx.save_for_backward(keep)
+        ctx.crit, ctx.shape = crit, (N, H, W)
+        crit._last = (weakref.ref(keep), (N, H, W))
+        return out.reshape(1, 1, 1, 1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        keep, = ctx.saved_tensors  # a second backward without retain_graph raises here, as torch does
+        lib = _native.load()
+        crit, (N, H, W) = ctx.crit, ctx.shape
+        dev = keep.device
+        grad_out = grad_out.detach().to(torch.float32).contiguous()
+        grad_x = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+        a = _native.LpipsBackwardArgs(size=C.sizeof(_native.LpipsBackwardArgs), N=N, H=H, W=W, debug=0,
+                                      packed_backward=crit._packed_backward_on(dev).data_ptr(), keep=keep.data_ptr(),
+                                      workspace=crit._workspace(dev, N, H, W).data_ptr(), grad_out=grad_out.data_ptr(),
+                                      grad_x=grad_x.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        if crit._backward_events is not None:
+            a.stage_events = crit._backward_events
+        with torch.cuda.device(dev):
+            rc = lib.fr_lpips_backward(C.byref(a))
+        if rc != 0:
+            raise RuntimeError(f"fovraster lpips_backward failed ({rc}): {_native.last_error()}")
+        return grad_x, None, None
+
+
+class LPIPSLoss(LPIPS):
+    """LPIPS as a training loss (see the module's text). ``forward(x, y)`` -> [1,1,1,1], with a ``grad_fn`` when x requires grad;
+    without, it is LPIPS's call: nothing is kept. ``activations()`` -> the 13 post-ReLU maps of x the last differentiable forward
+    kept."""
+
+    def __init__(self, net_type="vgg", version="0.1", weights=None):
+        super().__init__(net_type, version, weights)
+        self._packed_backward = {}  # device -> backward weights there
+        self._last = None           # (weak reference to the last kept state, (N, H, W))
+        self._forward_events = self._backward_events = None
+
+    def _packed_backward_on(self, dev):
+        p = self._packed_backward.get(dev)
+        if p is None:
+            p = self._packed_backward[dev] = pack_backward_weights(self._weights).to(dev)
+        return p
+
+    def forward(self, x, y):
+        if torch.is_tensor(y) and y.requires_grad:
+            raise RuntimeError("lpipsPyTorch: y requires grad, but y is the target of LPIPSLoss: the gradient is built with respect "
+                               "to x only (pass y.detach())")
+        if not (torch.is_tensor(x) and x.requires_grad):
+            return super().forward(x, y)
+        if not torch.is_grad_enabled():  # under torch.no_grad() there is nothing to differentiate
+            return super().forward(x.detach(), y)
+        self._check(x.detach(), y)
+        self._packed_backward_on(x.device)  # packed at the first differentiable call, not inside backward()
+        return _LPIPSFunction.apply(x, y, self)
+
+    def activations(self):
+        """the 13 post-ReLU maps of x from the last differentiable forward, [N,C_l,H_l,W_l] float32 copies (relu1_1 .. relu5_3).
+        The kept state lives as long as that forward's graph: call this before ``backward()`` frees it."""
+        if self._last is None:
+            raise RuntimeError("lpipsPyTorch: activations() needs a differentiable forward first (an x that requires grad)")
+        keep, (N, H, W) = self._last[0](), self._last[1]
+        if keep is None:
+            raise RuntimeError("lpipsPyTorch: the last differentiable forward's kept state is gone (backward() freed it); call "
+                               "activations() before backward(), or backward(retain_graph=True)")
+        lib = _native.load()
+        floats, out = keep.view(torch.float32), []
+        for l, (_, c) in enumerate(CONV_CHANNELS):
+            s = 0 if l < 2 else 1 if l < 4 else 2 if l < 7 else 3 if l < 10 else 4
+            h, w = H >> s, W >> s
+            off = lib.fr_lpips_keep_activation_offset(N, H, W, l) // 4
+            m = floats[off:off + N * c * h * w].view(N, c // 8, h, w, 8)
+            out.append(m.permute(0, 1, 4, 2, 3).reshape(N, c, h, w).clone())
+        return out
+
+    def stage_times(self, x, y):
+        """one keeping forward and its backward with an event between the stages -> ({stage: ms} over STAGES, {stage: ms} over
+        BACKWARD_STAGES) (synchronises; for tools/lpips_train_bench.py)"""
+        lib = _native.load()
+        self._forward_events, self._backward_events = _events(lib, len(STAGES) + 1), _events(lib, len(BACKWARD_STAGES) + 1)
+        try:
+            x = x.detach().clone().requires_grad_(True)
+            self(x, y).backward()
+            torch.cuda.synchronize(x.device)
+            return _elapsed(lib, self._forward_events, STAGES), _elapsed(lib, self._backward_events, BACKWARD_STAGES)
+        finally:
+            for e in list(self._forward_events) + list(self._backward_events):
+                lib.fr_event_destroy(e)
+            self._forward_events = self._backward_events = None
+
+
+def lpips_loss(x, y, net_type="vgg", version="0.1", weights=None):
+    """LPIPSLoss as a function: the criterion is kept per weights object, as ``lpips`` keeps its own."""
+    _check_net(net_type, version)
+    weights = _resolve(weights)
+    hit = _loss_cache.get(id(weights))
+    if hit is None or hit[0] is not weights:
+        hit = _loss_cache[id(weights)] = (weights, LPIPSLoss(net_type, version, weights=weights))
+    return hit[1](x, y)
 
 
 def lpips(x, y, net_type="alex", version="0.1", weights=None):

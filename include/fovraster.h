@@ -1048,6 +1048,69 @@ int fr_lpips_pack_weights(const float *const *conv_weights, const float *const *
 int64_t fr_lpips_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int fr_lpips_forward(const fr_lpips_args *args);
 
+/* LPIPS as a training loss: the forward that keeps what the backward needs, and the backward pass (csrc/lpips.hip; replaces
+ * lpipsPyTorch/modules/lpips.py, modules/networks.py and modules/utils.py run under torch.autograd -- lpips(render, gt).backward()).
+ * The gradient is that of fr_lpips_forward's value with respect to x, times an upstream scalar read on the device.
+ *   fr_lpips_backward_packed_bytes    the size of the backward weights, a blob of their own beside the packed weights.
+ *   fr_lpips_pack_backward_weights    a HOST routine, once per set of weights: conv_weights[13] as for fr_lpips_pack_weights into
+ *                                     `packed_backward` (host). Per layer 1 .. 12 the slabs of W'[ci,co,ky,kx] = W[co,ci,2-ky,2-kx]
+ *                                     (Cin' = Cout, Cout' = Cin) in the layout of the forward's slabs, [Cout'/64][Cin'/8] slabs of
+ *                                     [tap][group of 4][64][4]; in front of them the first layer's [chunk of 8][tap][8][3]. No bias.
+ *   fr_lpips_keep_workspace_bytes     the kept state of one differentiable forward over N pairs of H x W: x's 13 post-ReLU maps and
+ *                                     the five tap gradients (the gradient of the value with respect to x's tap maps, computed by
+ *                                     the forward's head pass, where both pictures' taps are in hand: y's maps are not kept).
+ *                                     3.25 GB for one 1080 x 1920 pair. -1 for sizes fr_lpips_forward refuses (fr_last_error).
+ *   fr_lpips_keep_activation_offset   the byte offset of layer 0 .. 12's map in the kept state, [N][C/8][H_l][W_l][8] floats
+ *                                     (channel c of a pixel at [c / 8] ... [c % 8]); -1 for a bad size or layer.
+ *   fr_lpips_forward_keep             fr_lpips_forward with x's maps written to `keep` (256-byte aligned, caller-owned, one per
+ *                                     call that is to be differentiated) instead of ping-ponging; `workspace` is that of
+ *                                     fr_lpips_workspace_bytes and holds nothing once the call has run. out[1] has the bits
+ *                                     fr_lpips_forward gives: the same kernels. stage_events: as fr_lpips_forward, [19].
+ *   fr_lpips_backward                 grad_x[N,3,H,W] (device, written whole) = grad_out[0] * d value / d x from `keep`.
+ *                                     grad_out: one device float, never read by the host. workspace: fr_lpips_workspace_bytes,
+ *                                     scratch. Rules: a ReLU passes the gradient where the kept output is > 0; a 2 x 2 pool sends
+ *                                     it to the window's first maximum in row-major order (torch's rules); at a pixel whose tap
+ *                                     vector is all zero the gradient is finite (the normalisation's second term is taken as 0,
+ *                                     its limit) where the reference's sqrt backward gives NaN. Exact f32 on the matrix cores, no
+ *                                     atomics: one bit pattern per element, run after run; equal pictures give exactly 0
+ *                                     everywhere. stage_events (optional [14]): in front of the pass and behind each of the 13
+ *                                     stages, the convolutions of the layers 12 .. 1 and the first layer's.
+ * Both calls run on `stream`, allocate nothing and never synchronise (debug != 0 does). FR_ERR_INVALID before anything is
+ * enqueued, the message names the field: size too small, N / H / W out of range as for fr_lpips_forward, a NULL pointer, a
+ * misaligned buffer. */
+typedef struct fr_lpips_keep_args {
+	uint32_t size;
+	int32_t N, H, W;
+	int32_t debug;
+	const float *x;
+	const float *y;
+	const void *packed;
+	void *workspace;
+	void *keep;
+	float *out;
+	float *out_taps;
+	void *stream;
+	void **stage_events;
+} fr_lpips_keep_args;
+typedef struct fr_lpips_backward_args {
+	uint32_t size;
+	int32_t N, H, W;
+	int32_t debug;
+	const void *packed_backward;
+	const void *keep;
+	void *workspace;
+	const float *grad_out;
+	float *grad_x;
+	void *stream;
+	void **stage_events;
+} fr_lpips_backward_args;
+size_t fr_lpips_backward_packed_bytes(void);
+int fr_lpips_pack_backward_weights(const float *const *conv_weights, void *packed_backward);
+int64_t fr_lpips_keep_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int64_t fr_lpips_keep_activation_offset(int32_t N, int32_t H, int32_t W, int32_t layer);
+int fr_lpips_forward_keep(const fr_lpips_keep_args *args);
+int fr_lpips_backward(const fr_lpips_backward_args *args);
+
 #ifdef __cplusplus
 }
 #endif
