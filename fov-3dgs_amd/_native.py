@@ -221,7 +221,9 @@ EXPORTS = ("fr_abi_version", "fr_last_error", "fr_event_create", "fr_event_destr
            "fr_forward_begin_aux", "fr_forward_aux_call",
            "fr_lpips_packed_bytes", "fr_lpips_pack_weights", "fr_lpips_workspace_bytes", "fr_lpips_forward",
            "fr_lpips_backward_packed_bytes", "fr_lpips_pack_backward_weights", "fr_lpips_keep_workspace_bytes",
-           "fr_lpips_keep_activation_offset", "fr_lpips_forward_keep", "fr_lpips_backward")
+           "fr_lpips_keep_activation_offset", "fr_lpips_forward_keep", "fr_lpips_backward",
+           "fr_hvs_metamer_workspace_floats", "fr_hvs_metamer", "fr_hvs_metamer_roundtrip",
+           "fr_hvs_metamer_loss_workspace_doubles", "fr_hvs_metamer_loss_forward", "fr_hvs_metamer_loss_backward")
 # added without an ABI bump: a library of the same ABI version built before them loads too (tools/ab_run.sh swaps libraries under one
 # Python); has_forward_ext() says which, and the callers fall back (rasterizer.py: visibility = radii > 0)
 EXT_EXPORTS = ("fr_forward_begin_ext", "fr_forward_ext_call")
@@ -314,6 +316,18 @@ def load():
     lib.fr_hvs_fov_backward.restype = C.c_int
     lib.fr_hvs_fov_backward_plan.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int64)]
     lib.fr_hvs_fov_backward_plan.restype = C.c_int
+    lib.fr_hvs_metamer_workspace_floats.argtypes = [C.c_int32] * 5
+    lib.fr_hvs_metamer_workspace_floats.restype = C.c_int64
+    lib.fr_hvs_metamer.argtypes = [C.c_int32] * 2 + [C.c_double] * 3 + [C.c_int32, C.c_double, C.c_double] + [C.c_int32] * 3 + [_FP] * 5 + [C.c_void_p]
+    lib.fr_hvs_metamer.restype = C.c_int
+    lib.fr_hvs_metamer_roundtrip.argtypes = [C.c_int32] * 5 + [_FP] * 4 + [C.c_void_p]
+    lib.fr_hvs_metamer_roundtrip.restype = C.c_int
+    lib.fr_hvs_metamer_loss_workspace_doubles.argtypes = [C.c_int64]
+    lib.fr_hvs_metamer_loss_workspace_doubles.restype = C.c_int64
+    lib.fr_hvs_metamer_loss_forward.argtypes = [C.c_int64, C.c_int32] + [_FP] * 4 + [C.c_void_p]
+    lib.fr_hvs_metamer_loss_forward.restype = C.c_int
+    lib.fr_hvs_metamer_loss_backward.argtypes = [C.c_int64, C.c_int32] + [_FP] * 4 + [C.c_void_p]
+    lib.fr_hvs_metamer_loss_backward.restype = C.c_int
     for n in ("fr_geometry_bytes",):
         getattr(lib, n).argtypes = [C.c_int32, C.c_int32]
         getattr(lib, n).restype = C.c_size_t

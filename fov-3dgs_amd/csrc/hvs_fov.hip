@@ -39,48 +39,19 @@
 //   k_fov_bwd_down  ... which also walks the adjoint of the area windows down the chain: level k collects from level k + 1.
 //   k_fov_bwd_map   per pixel of every map: its own term (floor(lod) = 0) plus level 1's windows, g_x = g_mean + 2 x g_square,
 //                   written to the workspace, from where k_hvs_bwd_level<FOV> / k_hvs_bwd_image<FOV> (hvs.hip) read it.
-#include "hvs_common.h"
+#include "hvs_fov_common.h"
 
 namespace fr {
 
-#define FOV_MAXK 16
-
-struct FovChain
-{
-	int K;                                        // the last level: always 1x1
-	int h[FOV_MAXK + 1], w[FOV_MAXK + 1];
-	long long m[FOV_MAXK + 1], q[FOV_MAXK + 1];   // offsets (floats) of [nmc,h_k,w_k] in a side's forward state, k >= 1
-};
-
-struct FovMaps { int h, w, nmc; long long maps; FovChain c; };
-
-struct FovLevel
-{
-	int nm;
-	FovMaps a;
-	long long low_in, low_out, lod;               // lod: offset in doubles
-	long long part; int part_n;
-	long long glow, g[FOV_MAXK + 1], gpart[FOV_MAXK + 1]; // backward workspace: [2,nmc,cells_k] and [S_k,2,nmc,cells_k]
-	int G[FOV_MAXK + 1], S[FOV_MAXK + 1], R[FOV_MAXK + 1];
-	int rows[FOV_MAXK + 1], cols[FOV_MAXK + 1];   // the footprint bound G, S and R were sized for (fr_hvs_fov_backward_plan reports it)
-};
-
-struct FovPlan
-{
-	int L, nb, H, W, lh, lw, nstats;
-	FovLevel lv[HVS_MAXL];
-	long long res_part; int res_part_n;
-	long long ws_floats, bwd_floats, n_partials, lod_doubles, lodmax, gmap;
-};
-
 static int fov_group(long long elems) { return elems <= 16 ? 1 : (elems <= 256 ? 8 : 64); }
 
-static int fov_plan(int H, int W, int L, int nb, FovPlan *p)
+// (the layout structures, fov_sample and fov_stat: hvs_fov_common.h, shared with csrc/metamer.hip)
+int fov_plan(const char *who, int H, int W, int L, int nb, FovPlan *p)
 {
-	if (L < 2 || L > HVS_MAXL) { set_error("hvs_fov: n_pyramid_levels %d outside 2..%d", L, HVS_MAXL); return FR_ERR_INVALID; }
-	if (nb < 1 || nb > HVS_MAXB) { set_error("hvs_fov: %d orientations outside 1..%d", nb, HVS_MAXB); return FR_ERR_INVALID; }
-	if (H <= 0 || W <= 0 || H % (1 << L) || W % (1 << L)) { set_error("hvs_fov: size %dx%d is not a multiple of 2^%d", H, W, L); return FR_ERR_INVALID; }
-	if (H > 16384 || W > 16384) { set_error("hvs_fov: size %dx%d too large (max 16384)", H, W); return FR_ERR_INVALID; }
+	if (L < 2 || L > HVS_MAXL) { set_error("%s: n_pyramid_levels %d outside 2..%d", who, L, HVS_MAXL); return FR_ERR_INVALID; }
+	if (nb < 1 || nb > HVS_MAXB) { set_error("%s: %d orientations outside 1..%d", who, nb, HVS_MAXB); return FR_ERR_INVALID; }
+	if (H <= 0 || W <= 0 || H % (1 << L) || W % (1 << L)) { set_error("%s: size %dx%d is not a multiple of 2^%d", who, H, W, L); return FR_ERR_INVALID; }
+	if (H > 16384 || W > 16384) { set_error("%s: size %dx%d too large (max 16384)", who, H, W); return FR_ERR_INVALID; }
 	p->L = L; p->nb = nb; p->H = H; p->W = W; p->nstats = 2 * (1 + (L - 1) * nb) + 1;
 	long long ws = 0, bw = 0, np = 0, nl = 0;
 	p->gmap = 0; bw += (long long)(nb + 1) * 3 * H * W; // the maps' gradients of one level at a time; level 0 is the largest
@@ -99,8 +70,8 @@ static int fov_plan(int H, int W, int L, int nb, FovPlan *p)
 		if (c.h[K] == 1 && c.w[K] == 2 && K < FOV_MAXK) { c.h[K + 1] = 1; c.w[K + 1] = 1; K++; }
 		if (c.h[K] != 1 || c.w[K] != 1)
 		{
-			set_error("hvs_fov: pyramid level %d (%dx%d): its mip chain ends at %dx%d, not at 1x1 or 1x2; the reference's MetamericLoss "
-				"fails on this size too (its final broadcast)", l, h, w, c.h[K], c.w[K]);
+			set_error("%s: pyramid level %d (%dx%d): its mip chain ends at %dx%d, not at 1x1 or 1x2; the reference's MetamericLoss "
+				"fails on this size too (its final broadcast)", who, l, h, w, c.h[K], c.w[K]);
 			return FR_ERR_INVALID;
 		}
 		c.K = K;
@@ -134,8 +105,6 @@ static int fov_plan(int H, int W, int L, int nb, FovPlan *p)
 }
 
 // ---------------------------------------------------------------- the LOD map
-struct FovLodArgs { int h, w, quadratic; double alpha, width, distance, gx, gy; double *lod; };
-
 // linspace(-.5, .5, n)[i], from the nearer end as torch steps it
 __device__ __forceinline__ double fov_lin(int i, int n)
 {
@@ -190,8 +159,6 @@ __global__ void __launch_bounds__(1024) k_fov_lodmax(const double *__restrict__ 
 }
 
 // ---------------------------------------------------------------- the mip chains
-struct FovMipArgs { int nmc, hs, ws, hd, wd, first; float *st[2]; long long ms, qs, md, qd; };
-
 // one chain step of every map: destination cell (jy, jx) = the mean over its adaptive window of the source level; first: the
 // source is the map itself and the square's source is x x, formed here in double
 __global__ void __launch_bounds__(256) k_fov_mip(FovMipArgs a)
@@ -218,52 +185,26 @@ __global__ void __launch_bounds__(256) k_fov_mip(FovMipArgs a)
 	st[a.qd + o] = (float)(q / cnt);
 }
 
-// ---------------------------------------------------------------- the blended statistics at one pixel
-// level k of map mc sampled at pixel (y, x): (mean, mean-square). Level 0 is the map (the bilinear sample at equal size is the
-// pixel itself) and its square is formed in double; level K is the constant.
-__device__ __forceinline__ void fov_sample(const float *__restrict__ st, const FovMaps &a, int mc, int k, int y, int x, double &M, double &Q)
+// ---------------------------------------------------------------- the launchers csrc/metamer.hip uses (hvs_fov_common.h)
+void fov_launch_lod(hipStream_t stream, const FovLodArgs &a)
 {
-	if (k == 0)
-	{
-		const double v = (double)st[a.maps + (size_t)mc * a.h * a.w + (size_t)y * a.w + x];
-		M = v; Q = v * v;
-		return;
-	}
-	const int hk = a.c.h[k], wk = a.c.w[k];
-	const size_t o = (size_t)mc * hk * wk;
-	const float *pm = st + a.c.m[k] + o, *pq = st + a.c.q[k] + o;
-	if (k == a.c.K) { M = (double)pm[0]; Q = (double)pq[0]; return; }
-	const HvsLerp ly = hvs_lerp(y, (double)hk / (double)a.h, hk), lx = hvs_lerp(x, (double)wk / (double)a.w, wk);
-	M = hvs_bilerp(pm, wk, ly, lx); Q = hvs_bilerp(pq, wk, ly, lx);
+	hipLaunchKernelGGL(k_fov_lod, dim3((unsigned)(((long long)a.h * a.w + 255) / 256)), dim3(256), 0, stream, a);
 }
 
-// (the maps hold no negative LOD; fov_lod_of keeps an index in range whatever the buffer holds)
-__device__ __forceinline__ double fov_lod_of(const double *__restrict__ lod, size_t i) { const double v = lod[i]; return v < 0.0 ? 0.0 : v; }
-
-__device__ __forceinline__ HvsStat fov_stat(const float *__restrict__ st, const FovMaps &a, int mc, int y, int x, double lod)
+void fov_launch_chain(hipStream_t stream, const FovMaps &a, float *st0, float *st1, int nside)
 {
-	double M, Q;
-	if (!(lod < (double)a.c.K))
-		fov_sample(st, a, mc, a.c.K, y, x, M, Q);
-	else
+	const FovChain &c = a.c;
+	for (int k = 0; k < c.K; k++)
 	{
-		const int l = (int)lod;
-		const double f = lod - (double)l;
-		fov_sample(st, a, mc, l, y, x, M, Q);
-		if (f != 0.0) // (f = 0: (1 - 0) a + 0 b = a in every precision)
-		{
-			double M1, Q1;
-			fov_sample(st, a, mc, l + 1, y, x, M1, Q1);
-			M = (1.0 - f) * M + f * M1; Q = (1.0 - f) * Q + f * Q1;
-		}
+		FovMipArgs m;
+		m.nmc = a.nmc; m.hs = c.h[k]; m.ws = c.w[k]; m.hd = c.h[k + 1]; m.wd = c.w[k + 1]; m.first = k == 0;
+		m.st[0] = st0; m.st[1] = st1;
+		m.ms = k == 0 ? a.maps : c.m[k]; m.qs = k == 0 ? a.maps : c.q[k]; m.md = c.m[k + 1]; m.qd = c.q[k + 1];
+		hipLaunchKernelGGL(k_fov_mip, dim3((unsigned)(((long long)m.hd * m.wd + 255) / 256), a.nmc, nside), dim3(256), 0, stream, m);
 	}
-	HvsStat s;
-	s.mean = M;
-	s.var = Q - M * M;
-	s.std = sqrt(s.var < HVS_VAR_FLOOR ? HVS_VAR_FLOOR : s.var);
-	return s;
 }
 
+// ---------------------------------------------------------------- the blended statistics at one pixel: fov_stat (hvs_fov_common.h)
 struct FovCmpArgs { FovMaps a; int mse; float wgt; const float *wsi, *wst; const double *lod; float *partials; };
 
 __global__ void __launch_bounds__(256) k_fov_cmp(FovCmpArgs a)
@@ -437,13 +378,18 @@ static int fov_check(int Hs, int Ws, int H, int W, double alpha, double width, d
 		int rc = hvs_resize_check(Hs, Ws, H, W);
 		if (rc != FR_OK) return rc;
 	}
-	if (!(alpha >= 0.0) || !(alpha < 1e6)) { set_error("hvs_fov: alpha must be finite and not negative"); return FR_ERR_INVALID; }
+	return fov_check_view("hvs_fov", alpha, width, distance, gx, gy);
+}
+
+int fov_check_view(const char *who, double alpha, double width, double distance, double gx, double gy)
+{
+	if (!(alpha >= 0.0) || !(alpha < 1e6)) { set_error("%s: alpha must be finite and not negative", who); return FR_ERR_INVALID; }
 	if (!(width > 0.0) || !(width < 1e9) || !(distance > 0.0) || !(distance < 1e9))
 	{
-		set_error("hvs_fov: real_image_width and real_viewing_distance must be positive and finite");
+		set_error("%s: real_image_width and real_viewing_distance must be positive and finite", who);
 		return FR_ERR_INVALID;
 	}
-	if (!(fabs(gx) < 1e6) || !(fabs(gy) < 1e6)) { set_error("hvs_fov: the gaze must be finite"); return FR_ERR_INVALID; }
+	if (!(fabs(gx) < 1e6) || !(fabs(gy) < 1e6)) { set_error("%s: the gaze must be finite", who); return FR_ERR_INVALID; }
 	return FR_OK;
 }
 
@@ -455,7 +401,7 @@ extern "C" int64_t fr_hvs_fov_workspace_floats(int32_t Hs, int32_t Ws, int32_t H
 {
 	FovPlan p;
 	if ((Hs || Ws) && hvs_resize_check(Hs, Ws, H, W) != FR_OK) return -1;
-	if (fov_plan(H, W, n_levels, n_orientations, &p) != FR_OK) return -1;
+	if (fov_plan("hvs_fov", H, W, n_levels, n_orientations, &p) != FR_OK) return -1;
 	const bool resized = (Hs || Ws) && !(Hs == H && Ws == W);
 	if (which == 0) return p.ws_floats;
 	if (which == 1) return p.bwd_floats + (resized ? 3ll * H * W : 0);
@@ -468,7 +414,7 @@ extern "C" int64_t fr_hvs_fov_workspace_floats(int32_t Hs, int32_t Ws, int32_t H
 extern "C" int fr_hvs_fov_backward_plan(int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t level, int32_t k, int64_t *out)
 {
 	FovPlan p;
-	if (fov_plan(H, W, n_levels, n_orientations, &p) != FR_OK) return FR_ERR_INVALID;
+	if (fov_plan("hvs_fov", H, W, n_levels, n_orientations, &p) != FR_OK) return FR_ERR_INVALID;
 	if (level < 0 || level > p.L - 2) { set_error("hvs_fov_backward_plan: pyramid level %d outside 0..%d", level, p.L - 2); return FR_ERR_INVALID; }
 	const FovLevel &v = p.lv[level];
 	if (k < 1 || k > v.a.c.K) { set_error("hvs_fov_backward_plan: chain level %d outside 1..%d (pyramid level %d)", k, v.a.c.K, level); return FR_ERR_INVALID; }
@@ -486,7 +432,7 @@ extern "C" int fr_hvs_fov_forward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, 
 	FovPlan p;
 	int rc = fov_check(Hs, Ws, H, W, alpha, real_image_width, real_viewing_distance, gaze_x, gaze_y);
 	if (rc != FR_OK) return rc;
-	if ((rc = fov_plan(H, W, n_levels, n_orientations, &p)) != FR_OK) return rc;
+	if ((rc = fov_plan("hvs_fov", H, W, n_levels, n_orientations, &p)) != FR_OK) return rc;
 	if (mode != 0 && mode != 1) { set_error("hvs_fov: mode must be 0 (linear) or 1 (quadratic)"); return FR_ERR_INVALID; }
 	if (!filters || !img || !state_img || !state_target || !lod || !partials || !out) { set_error("hvs_fov_forward: a required pointer is null"); return FR_ERR_INVALID; }
 	if ((uintptr_t)lod & 7) { set_error("hvs_fov_forward: lod must be 8-byte aligned (it holds doubles)"); return FR_ERR_INVALID; }
@@ -514,15 +460,7 @@ extern "C" int fr_hvs_fov_forward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, 
 		a.low_in = v.low_in; a.maps = v.a.maps; a.low_out = v.low_out; a.filt = filters;
 		a.hs = Hs; a.wsrc = Ws; a.ry = Hs ? (double)Hs / (double)H : 1.0; a.rx = Hs ? (double)Ws / (double)W : 1.0;
 		hvs_launch_level(l == 0 && Hs, dim3((w + HVS_T - 1) / HVS_T, (h + HVS_T - 1) / HVS_T, 3 * nside), stream, a);
-		const FovChain &c = v.a.c;
-		for (int k = 0; k < c.K; k++)
-		{
-			FovMipArgs m;
-			m.nmc = v.a.nmc; m.hs = c.h[k]; m.ws = c.w[k]; m.hd = c.h[k + 1]; m.wd = c.w[k + 1]; m.first = k == 0;
-			m.st[0] = state_img; m.st[1] = state_target;
-			m.ms = k == 0 ? v.a.maps : c.m[k]; m.qs = k == 0 ? v.a.maps : c.q[k]; m.md = c.m[k + 1]; m.qd = c.q[k + 1];
-			hipLaunchKernelGGL(k_fov_mip, dim3((unsigned)(((long long)m.hd * m.wd + 255) / 256), v.a.nmc, nside), dim3(256), 0, stream, m);
-		}
+		fov_launch_chain(stream, v.a, state_img, state_target, nside);
 		FovCmpArgs q;
 		q.a = v.a; q.mse = mse; q.wgt = wstat / (float)(3 * plane); q.wsi = state_img; q.wst = state_target; q.lod = lodd + v.lod;
 		q.partials = partials + v.part;
@@ -541,7 +479,7 @@ extern "C" int fr_hvs_fov_backward(int32_t Hs, int32_t Ws, int32_t H, int32_t W,
 	FovPlan p;
 	int rc = fov_check(Hs, Ws, H, W, alpha, real_image_width, real_viewing_distance, gaze_x, gaze_y);
 	if (rc != FR_OK) return rc;
-	if ((rc = fov_plan(H, W, n_levels, n_orientations, &p)) != FR_OK) return rc;
+	if ((rc = fov_plan("hvs_fov", H, W, n_levels, n_orientations, &p)) != FR_OK) return rc;
 	if (!filters || !state_img || !state_target || !lod || !workspace || !dL_dimg) { set_error("hvs_fov_backward: a required pointer is null"); return FR_ERR_INVALID; }
 	if ((uintptr_t)lod & 7) { set_error("hvs_fov_backward: lod must be 8-byte aligned (it holds doubles)"); return FR_ERR_INVALID; }
 	if (Hs == H && Ws == W) Hs = Ws = 0;

@@ -37,7 +37,8 @@ the same settings (the resize size among them), colour space and device (rasteri
 launches as the image's. There is no host synchronisation in the call.
 
 ``MetamericLoss`` (metameric_loss.py, csrc/hvs_fov.hip) is the gaze-dependent loss of the same package: its docstring says what
-it supports.
+it supports. ``MetamerMSELoss`` (metamer_mse_loss.py, csrc/metamer.hip) is the third name of the reference's import line: it
+synthesises a metamer of the target and compares against that picture; ``pyramid_roundtrip`` is its synthesis alone.
 """
 import importlib
 import math
@@ -47,7 +48,7 @@ import torch
 
 from . import _native_hvs as _hvs
 
-__all__ = ["MetamericLossUniform", "MetamericLoss", "pyramid_size"]
+__all__ = ["MetamericLossUniform", "MetamericLoss", "MetamerMSELoss", "pyramid_size", "pyramid_roundtrip"]
 
 
 def pyramid_size(height, width, n_pyramid_levels):
@@ -204,3 +205,4 @@ class MetamericLossUniform:
 
 
 from .metameric_loss import MetamericLoss  # noqa: E402  (it uses pack_filters and _resize_size from above)
+from .metamer_mse_loss import MetamerMSELoss, pyramid_roundtrip  # noqa: E402

@@ -657,6 +657,43 @@ int fr_hvs_fov_backward(int32_t Hs, int32_t Ws, int32_t H, int32_t W, double alp
 	int32_t mode, double gaze_x, double gaze_y, int32_t n_levels, int32_t n_orientations, int32_t mse, int32_t rgb, const float *filters,
 	const float *state_img, const float *state_target, const float *lod, float *workspace, const float *grad_scale, float *dL_dimg, void *stream);
 
+/* The metamer of a target at a gaze, fused (csrc/metamer.hip): MetamerMSELoss with avg_pooling_downup=True (the bilinear
+ * pyramid of the two losses above), equi=False and the cropped 5x5 filters -- the steerable pyramid's SYNTHESIS, which the two
+ * losses above never need. filters, mode, gaze, alpha and the display geometry are fr_hvs_fov_forward's; the sizes it refuses are
+ * refused here (H, W multiples of 2^n_levels, n_levels 2..6, n_orientations 1..8, every level's mip chain ending at 1x1 or 1x2).
+ * fr_hvs_metamer replaces MetamerMSELoss.gen_metamer (metamer/odak_perception/metamer_mse_loss.py:63-123) and what it calls:
+ *   MetamericLoss.calc_statsmaps (metameric_loss.py:86-167), construct_pyramid (spatial_steerable_pyramid.py:132-180) of target
+ *   and noise, match_level (metamer_mse_loss.py:97-107), reconstruct_from_pyramid (spatial_steerable_pyramid.py:182-223) and
+ *   ycrcb_2_rgb (color_conversion.py:424-427).
+ *   target [3,H,W]: rgb = 1 RGB (converted as rgb_2_ycrcb does), 0 = already YCrCb. noise [3,H,W]: the picture whose pyramid is
+ *   matched, used as it is (the reference draws rand_like of the YCrCb target). out [3,H,W]: the metamer in RGB, not clamped.
+ *   h and every oriented band of the noise's pyramid become (band - mean) / max(rms, 1e-6) * std(y, x) + mean(y, x): ONE mean and
+ *   ONE root mean square of the centred values per band, over its three channels, summed in double in a fixed order (partials
+ *   per workgroup, one finishing workgroup); std and mean the target's blended statistics at the pixel, as the foveated loss
+ *   forms them (variance floored at 1e-7), evaluated in the matching kernel. The last lowpass is the target's.
+ *   Everything is enqueued on `stream`: no host synchronisation, no allocation, no float atomics, the same bits on every run.
+ * fr_hvs_metamer_roundtrip replaces reconstruct_from_pyramid(construct_pyramid(x)) (spatial_steerable_pyramid.py:132-223): the
+ *   synthesis from the picture's own pyramid, no noise and no matching. rgb = 1: x is RGB, converted on the way in and back on
+ *   the way out; 0: the three channels as they are.
+ * fr_hvs_metamer_workspace_floats(.., roundtrip): floats of the caller-owned workspace (8-byte aligned: it starts with doubles)
+ *   of fr_hvs_metamer (roundtrip = 0) or fr_hvs_metamer_roundtrip (1); -1 for bad arguments.
+ * The loss, MetamerMSELoss.__call__'s torch.nn.L1Loss / MSELoss (metamer_mse_loss.py:146-152; mse = 0 / 1) over n = 3 H W elements:
+ *   forward:  one launch. out[0] = mean |image - metamer| or mean (image - metamer)^2, summed in double in a fixed order.
+ *             workspace: fr_hvs_metamer_loss_workspace_doubles(n) doubles, ZERO before the first use; every call leaves the one
+ *             word it needs zero (the last one) zero again, so the buffer serves call after call on one stream.
+ *   backward: one elementwise launch. dL_dimage = grad_scale[0] (a device scalar; NULL = 1) times sign(d) / n or 2 d / n.
+ * Every malformed argument is FR_ERR_INVALID before anything is enqueued; fr_last_error names the argument. */
+int64_t fr_hvs_metamer_workspace_floats(int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t roundtrip);
+int fr_hvs_metamer(int32_t H, int32_t W, double alpha, double real_image_width, double real_viewing_distance, int32_t mode,
+	double gaze_x, double gaze_y, int32_t n_levels, int32_t n_orientations, int32_t rgb, const float *filters, const float *target,
+	const float *noise, float *workspace, float *out, void *stream);
+int fr_hvs_metamer_roundtrip(int32_t H, int32_t W, int32_t n_levels, int32_t n_orientations, int32_t rgb, const float *filters,
+	const float *image, float *workspace, float *out, void *stream);
+int64_t fr_hvs_metamer_loss_workspace_doubles(int64_t n);
+int fr_hvs_metamer_loss_forward(int64_t n, int32_t mse, const float *image, const float *metamer, double *workspace, float *out, void *stream);
+int fr_hvs_metamer_loss_backward(int64_t n, int32_t mse, const float *image, const float *metamer, const float *grad_scale,
+	float *dL_dimage, void *stream);
+
 /* Mean squared distance of every point to its three nearest neighbours: simple-knn's distCUDA2, the initial scale of
  * GaussianModel.create_from_pcd (replaces SimpleKNN::knn, fov3dgs/submodules/simple-knn/simple_knn.cu:185-220, as called by
  * distCUDA2, spatial.cu:15-25). points: [P,3] fp32 device array; mean_dist2: [P] fp32, written in full:
