@@ -4,7 +4,8 @@ Follows fov3dgs/utils/loss_utils.py: l1_loss :17-18; gaussian / create_window :2
 1-D window, 2-D window = outer product); _ssim :57-76 (five zero-padded grouped correlations, C1 = 0.01^2,
 C2 = 0.03^2, mean of the map). Written with explicit shifted sums in float64 (no conv2d), gradients by autograd.
 Pinned against the reference itself: tests/golden/ref_loss.npz and ref_loss2.npz were produced by importing
-loss_utils.py in the build container (tests/golden/make_golden.py, make_loss_golden.py).
+loss_utils.py in the build container (tests/golden/make_golden.py, make_loss_golden.py). On flat, dark and stepped pictures it is
+the float64 reference point of tests/loss_cases.py, beside the reference's own float32 results (ref_loss3.npz).
 """
 from math import exp
 

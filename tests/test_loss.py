@@ -1,5 +1,11 @@
 """Image losses: the oracle against vectors made by the reference's own loss_utils.py (CPU),
-and the fused HIP kernels against both (GPU)."""
+and the fused HIP kernels against both (GPU).
+
+The fixed tolerances of this file (2e-6 / 3e-6 absolute on values; rtol 1e-4 .. 2e-4 with atol 2e-7 + 1e-5 / n on gradients) hold on
+what its pictures are: white noise, where the local variance and mean^2 swamp SSIM's stabilisers C1, C2 and E[x^2] - mu^2 cancels
+nothing. They are no statement about flat, dark or stepped pictures -- there the reference's own float32 is up to 2.2e-4 from float64
+in SSIM -- and they cannot see a wrong stabiliser (C1 doubled moves these cases by 5e-8). tests/loss_cases.py, test_loss_flat_cpu.py
+and test_loss_flat_gpu.py judge the same kernels on such pictures, by the spread of a float32 family of the reference's formula."""
 import os
 
 import numpy as np
@@ -41,7 +47,9 @@ def _need_gpu():
 @pytest.mark.gpu
 def test_hip_losses_match_reference_vectors():
     """Tolerances: values 2e-6 absolute (fp32 separable sums vs the reference's fp32 121-tap convolutions), gradients
-    1e-4 relative + 2e-7 absolute."""
+    1e-4 relative + 2e-7 absolute. True of these noise vectors (and the one 70x33 smooth pair), not of pictures in general: on
+    tests/loss_cases.py's flat and stepped pairs the reference's fp32 value is itself 3e-6 .. 2.2e-4 from float64, and the kernels are
+    judged against float64 by that spread instead (measured on the MI355X: 9.3e-6 and 3.7e-7; profiles/loss_parity.json)."""
     _need_gpu()
     from fov3dgs_amd import loss_utils as lu
     for name, a, b, l1, ss, loss, grad, ssim_grad in _cases():

@@ -2,8 +2,11 @@
 against tests/golden/ref_quality.npz -- the reference's own loss_utils.ssim, l1_loss and image_utils.psnr, mse on four pictures,
 none a multiple of the kernels' 16x32 tile but the last, with the same expressions evaluated in float64 beside them.
 
-Tolerances: SSIM and L1 within 2e-6 absolute of the reference's fp32 value (what tests/test_loss.py holds the same arithmetic
-to); MSE within 1e-6 relative of the float64 evaluation (non-negative terms, accumulated in double); PSNR within 1e-5 dB of
+Tolerances: SSIM and L1 within 2e-6 absolute of the reference's fp32 value on THESE pictures: noise, and one smooth pair with
+noise of sigma 0.03 (what tests/test_loss.py holds the same arithmetic to, on the same kind of picture). It is no general bound: on flat, dark and stepped pictures the
+reference's fp32 SSIM is itself up to 2.2e-4 from float64, and tests/test_loss_flat_gpu.py judges the meter there against float64 by
+the spread of a float32 family of the reference's formula (measured: 9.9e-7 blob, 9.3e-6 flat, 3.7e-7 steps, 3.3e-8 dark, each with
+the bits of loss_utils.ssim; profiles/loss_parity.json); MSE within 1e-6 relative of the float64 evaluation (non-negative terms, accumulated in double); PSNR within 1e-5 dB of
 it (10 / ln 10 times the MSE bound, and an fp32 rounding of a value below 64 dB is under 4e-6), and within 1e-5 dB plus the
 reference's own fp32-to-float64 distance (stored by the generator) of the reference's fp32 value."""
 import os
